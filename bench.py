@@ -11,7 +11,15 @@ the timed region.
   N  > 1 : tensor-parallel shards (heads / ffn columns) with an all-reduce (RCCL over xGMI) on the
            residual stream after o_proj and down_proj ("scaling": "strong": the same model, N GPUs).
 
-Extra objects on the JSON line (rank 0, N = 1):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line: metric, value,
+unit, higher_is_better, dtype, ms_per_step (one timed step), plus figures derived from that timing without further GPU work.
+--dump-outputs DIR also writes what the timed call returned and what its last step computed (DIR/ids.npy: the N greedy ids
+as float64, DIR/logits.npy: the last step's logits as float32); the inputs are seeded, identical from run to run.
+
+Extra objects on the JSON line (rank 0, N = 1, only with --full):
+  "decode_512"   the same metric over BASELINE cfg2's own 512 decoded tokens when --steps differs
+  "layer_split" / "kernels" / "ceilings"   per-launch prologue / rows / boundary times, the per-launch kernel table, measured read and GEMM ceilings
+  "host_cores"   cores this process may run on
   "roofline"     the dominant kernel (the gate|up GEMV): HIP events on the launch stream; "traffic" = HBM bytes per launch from a separate rocprofv3 --pmc FETCH_SIZE
                  pass that bench.py spawns over the same kernel (--no-pmc: null)
   "cpu_baseline" the reference HOST itself (oracle/_ref/ref_chat = chatllm.cpp's graph builder + ggml scheduler + CPU backend, compiled from
@@ -548,7 +556,15 @@ def main():
     ap.add_argument("--no-full-depth-parity", action="store_true", help="with --dropin-cfg4 / --dropin-cfg5: skip the CPU-host-vs-module comparison of ids and logit words over ALL layers")
     ap.add_argument("--dry-run-shards", action="store_true", help="shape math of the N-rank tensor-parallel shards only (no GPU, no weights): one JSON object, then exit")
     ap.add_argument("--no-graph", action="store_true", help="launch the fused decode kernels eagerly (for rocprofv3 kernel traces)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else the line can carry (N = 1: decode_512, roofline with its PMC pass, "
+                    "layer_split, kernels, ceilings, cpu_baseline, dropin, other_types, prefill); the --no-* and --dropin-* options refine it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the ids the timed call returned (ids.npy, float64) and its last step's logits "
+                    "(logits.npy, float32) into DIR")
     args = ap.parse_args()
+    if (args.dropin_cfg5 or args.dropin_cfg4) and not args.full:
+        ap.error("--dropin-cfg5 / --dropin-cfg4 are measurements of --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -761,6 +777,11 @@ def main():
         tmax = torch.tensor([dt], device=f"cuda:{local}")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what the timed call returned (its greedy ids) and what its last step computed (the logits those ids' last arg-max was taken over)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), np.asarray(out, np.float64))
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), m.debug_read("logits", cfg["vocab"]).astype(np.float32))
 
     res = {
         "metric": "decode tokens/s", "value": args.steps / dt, "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
@@ -779,7 +800,7 @@ def main():
         res["model_hbm_frac"] = bytes_tok * res["value"] / (HBM_PEAK_GBS * 1e9) / world
         res["algorithmic_bytes_per_token"] = bytes_tok
         res["greedy_tail"] = [int(t) for t in out[-4:]]
-        if world == 1:
+        if world == 1 and args.full:
             if args.steps != cfg2_steps and args.model == "llama3-8b":
                 # the same metric at BASELINE cfg2's own length (16-token prompt, 512 decoded tokens: n_ctx 32 -> 544), whatever --steps the caller timed
                 try:

@@ -165,3 +165,34 @@ def test_gpu_whole_model_against_the_reference_host(gpu, t, name):
             if s < 12:
                 lg = m.decode_fused_logits(int(ids[s])) if fused else m.forward([int(ids[s])])
         m.close()
+
+
+# ---------------------------------------------------------------- CPU: the packed IQ codebooks vs the reference's tables
+IQG = np.load(os.path.join(os.path.dirname(__file__), "golden", "iq_grids_reference.npz"))      # ggml-common.h's grids, entry for entry (tests/golden/make_iq_grids_golden.py)
+
+
+def test_packed_codebooks_decode_to_the_reference_grids():
+    """chatllm.cpp_amd/csrc/iq_grids.h keeps the IQ1 / IQ2 / IQ3 codebooks as one uint16 per entry (base-3 digits / 3-bit levels); decoded the way iq_grids.h decodes them they
+    must be the reference's tables entry for entry (ggml-common.h:528-1615) -- and the sign table must be 7 bits + even parity"""
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "chatllm.cpp_amd", "csrc", "iq_grids.h")).read()
+
+    def ref_table(name):
+        return [int(v) for v in IQG[name]]
+
+    def codes(name):
+        m = re.search(r"%s\[\d+\] = \{(.*?)\};" % name, hdr, re.S)
+        return [int(x) for x in re.findall(r"\d+", m.group(1))]
+
+    def iq2(code):
+        v = 0
+        for k in range(8):
+            t = (code // 3 ** k) % 3
+            v |= (8 + 17 * t + (t >> 1)) << (8 * k)
+        return v
+    for name, cname in (("iq2xxs_grid", "IQ2XXS_CODE"), ("iq2xs_grid", "IQ2XS_CODE"), ("iq2s_grid", "IQ2S_CODE")):
+        assert [iq2(c) for c in codes(cname)] == ref_table(name), name
+    assert [sum((62 if ((c >> (3 * k)) & 7) == 7 else 4 + 8 * ((c >> (3 * k)) & 7)) << (8 * k) for k in range(4)) for c in codes("IQ3XXS_CODE")] == ref_table("iq3xxs_grid")
+    assert [sum((1 + 2 * ((c >> (3 * k)) & 7)) << (8 * k) for k in range(4)) for c in codes("IQ3S_CODE")] == ref_table("iq3s_grid")
+    assert [sum((((c // 3 ** k) % 3 - 1) & 0xff) << (8 * k) for k in range(8)) for c in codes("IQ1S_CODE")] == ref_table("iq1s_grid")
+    assert ref_table("ksigns_iq2xs") == [i | ((bin(i).count("1") & 1) << 7) for i in range(128)]
