@@ -105,7 +105,7 @@ __device__ __forceinline__ f32x4 tpf_gather4(const tp_fuse_dev * cx, const char 
 // 18 / 20 / 34-byte block, activation quantized to Q8_0 / Q8_1).  nblk = weight blocks per row.
 // MOE (MUL_MAT_ID for one token, ggml_compute_forward_mul_mat_id ggml-cpu.c:1432-1678): blockIdx.y is the slot; the slot's expert comes from
 // device memory (ids[slot], the TOP_K node's output), W / px / dst move by the slot: dst[:, slot] = W[:, :, ids[slot]]^T . x[:, slot or 0]
-// FREE (gemv_free32.hip only, the 32-weight block formats): the opt-in free-order tier -- q32_block_free instead of the chain records; every other instantiation is untouched
+// FREE (gemv_free32.hip only; Q4_0 / Q4_1 / Q8_0, never Q4_K): the opt-in free-order tier -- q32_block_free instead of the chain records; every other instantiation is untouched
 template <int FMT, int PRO, int EPI, int NPRE, bool MOE = false, bool FREE = false>
 __global__ void __launch_bounds__(1024) k_gemv_dec(const float * __restrict__ px, const float * __restrict__ pw, const float * __restrict__ padd,
                                                         const char * __restrict__ W, int nblk, int kfull, int nrem, float eps,
@@ -115,6 +115,7 @@ __global__ void __launch_bounds__(1024) k_gemv_dec(const float * __restrict__ px
     // (EPI 2 reuses two parameters the non-MOE forms leave idle -- ids: where the TOP_K indices go, dst_slot_stride: k -- and keeps its 2 x 64 floats behind the
     //  chain records in the dynamic LDS, so that the kernel-argument block and the static LDS of every other instantiation stay what they were: a 16-byte
     //  longer argument block + 8 bytes of static LDS measured +2..4 % on all of them)
+    static_assert(!(FREE && FMT == CLLM_TYPE_Q4_K), "k_gemv_dec: the free-order tier is for the 32-weight block formats; Q4_K has the exact order only");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     // ---- the argument slots BY FAMILY.  The physical signature is one and the same for every instantiation (its size and order are part of the tuned launch, see above); what a
     //      slot means in a family is said HERE, once, and the code below uses these names only: ----
@@ -484,8 +485,7 @@ __global__ void __launch_bounds__(1024) k_gemv_dec(const float * __restrict__ px
             const bool ok = ck < nmine && b < nblk;
             const char * arow = EPI == 3 ? lds + csub * arb : lds;
             if (IS_K) {
-                if constexpr (FREE) acc = acc + q4k_block_free4(hh[p], qq[p], q2[(IS_Q8 || IS_K) ? p : 0], arow, off_d, off_s, ok ? b : 0, ok, L);
-                else q4k_emit4(hh[p], qq[p], q2[(IS_Q8 || IS_K) ? p : 0], arow, off_d, off_s, ok ? b : 0, ok, L, chain);
+                q4k_emit4(hh[p], qq[p], q2[(IS_Q8 || IS_K) ? p : 0], arow, off_d, off_s, ok ? b : 0, ok, L, chain);
             } else {
                 uint32_t h; u32x4 w0, w1 = {0, 0, 0, 0};
                 q32_align<IS_K ? CLLM_TYPE_Q4_0 : FMT>(qq[p], q2[IS_Q8 ? p : 0], hh[p].x, hh[p].y, h, w0, w1);

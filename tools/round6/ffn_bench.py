@@ -1,7 +1,7 @@
-#!/usr/bin/env python3
+# NEEDS tools/round6/ffn_fused_launch.patch APPLIED (git apply tools/round6/ffn_fused_launch.patch, then make -C chatllm.cpp_amd/csrc): the fused launch is a closed experiment, not in the library.
 """The decode step's FFN block (Llama-3-8B shapes, Q4_K) as the two launches of the five-launch layer against ONE fused launch (ffn_fused.hip) and against the fused launch
 with a hand-off that costs nothing (the bound): HIP-event time per block over weight copies cycled past the Infinity Cache, then the fused launch's in-kernel stamps.
-usage: python tools/ffn_bench.py [--iters 64] [--no-stamps]"""
+usage: python tools/round6/ffn_bench.py [--iters 64] [--no-stamps]"""
 import argparse
 import ctypes as C
 import os
@@ -9,7 +9,7 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 

@@ -1,4 +1,5 @@
 #!/bin/bash
+# (record of a past call: the fused FFN launch (and tools/ffn_bench.py, now tools/round6/ffn_bench.py) left the library afterwards -- tools/round6/ffn_fused_launch.patch restores it)
 # round 6, call 2: the fused FFN launch (ffn_fused.hip) -- parity tests, the block's time against the two launches and against the null hand-off, the decode step with it on / off
 O=gpurun_out/r6_2; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_llama.py -x -q -m gpu -k "fused_ffn or fused_decode_path or greedy" 2>&1 | tail -15 | tee $O/pytest_ffn.txt

@@ -1,4 +1,5 @@
 #!/bin/bash
+# (record of a past call: the =2 value of the switch left the library afterwards -- tools/round6/q4k_free_order_pricing.patch restores it)
 # round 6, call 20: what the reference's accumulation ORDER costs the headline (Q4_K) decode: the same kernels with the free fp32 fold (CLLM_DECODE_FREE_ORDER=2: a pricing
 # experiment, never a product path -- the logits are far off), step rate and the per-launch table, against the default
 O=gpurun_out/r6_20; mkdir -p $O

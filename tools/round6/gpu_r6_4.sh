@@ -1,4 +1,5 @@
 #!/bin/bash
+# (record of a past call: the fused FFN launch (and tools/ffn_bench.py, now tools/round6/ffn_bench.py) left the library afterwards -- tools/round6/ffn_fused_launch.patch restores it)
 # round 6, call 4: fused FFN, final form of the experiment (ring filled behind the prologue barrier; the edge polled in its FIFO slot)
 O=gpurun_out/r6_4; mkdir -p $O
 timeout 600 python -m pytest tests/test_gpu_llama.py -x -q -m gpu -k "fused_ffn" 2>&1 | tail -5 | tee $O/pytest_ffn.txt
