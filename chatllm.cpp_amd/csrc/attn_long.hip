@@ -375,7 +375,7 @@ int launch_attn_long(hipStream_t st, const float * qkv, const int32_t * pos_dev,
 #define SC3(HD_) do { if (r2 == 1) SC2(HD_, 1); else if (r2 == 2) SC2(HD_, 2); else if (r2 == 4) SC2(HD_, 4); else SC2(HD_, 8); } while (0)
     if (hd == 128) SC3(128); else SC3(64);
     LAUNCH_CHECK();
-    static const bool no_fuse = getenv("CLLM_ATTN_LONG_3") && atoi(getenv("CLLM_ATTN_LONG_3")) == 1;      // (tools: the three-launch form at every length)
+    static const bool no_fuse = opt_int(OPT_CLLM_ATTN_LONG_3) == 1;      // (tools: the three-launch form at every length)
     if (ML <= AL_FUSED_MAX_ML && ML % 32 == 0 && !no_fuse) {                       // soft_max inside the V.P launch
         const size_t lds2 = (size_t) ML * 4 + (size_t)(ML / 8) * 4 + (size_t) ML * 2 + 4 * AL_NS * 4096;
 #define PV2(HD_) do { \

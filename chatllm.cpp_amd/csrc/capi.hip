@@ -27,6 +27,20 @@ int cllm_hip_check(hipError_t e, const char * what, const char * file, int line)
 extern "C" const char * cllm_last_error(void) { return g_err; }
 extern "C" int cllm_abi_version(void) { return 1; }
 
+// ---- the switches by name (options.h), for hosts that link only this ABI.  A name that is not registered or is asked for as the wrong kind is the caller's bug:
+//      0 / NULL and the error text, as FAIL does.  The library's own call sites use the accessors of options.h. ----
+static int option_id(const char * name, int kind, const char * fn) {
+    const int id = opt_find(name);
+    if (id < 0) FAIL(-1, "%s: %s is not a registered switch (csrc/options.def)", fn, name ? name : "(null)");
+    if (kind >= 0 && opt_kind((cllm_opt) id) != kind) FAIL(-1, "%s: %s is not of that kind (csrc/options.def)", fn, name);
+    return id;
+}
+extern "C" int cllm_option_is_set(const char * name) { const int id = option_id(name, -1, "option_is_set"); return id >= 0 && opt_is_set((cllm_opt) id); }
+extern "C" int cllm_option_int(const char * name) { const int id = option_id(name, OPT_KIND_INT, "option_int"); return id < 0 ? 0 : opt_int((cllm_opt) id); }
+extern "C" double cllm_option_real(const char * name) { const int id = option_id(name, OPT_KIND_REAL, "option_real"); return id < 0 ? 0.0 : opt_real((cllm_opt) id); }
+extern "C" const char * cllm_option_str(const char * name) { const int id = option_id(name, OPT_KIND_WORD, "option_str"); return id < 0 ? nullptr : opt_str((cllm_opt) id); }
+extern "C" size_t cllm_options_describe(char * buf, size_t size) { return opt_describe(buf, size); }
+
 // ---- type traits (ggml.c type_traits[]) -------------------------------------------------------------------
 extern "C" size_t cllm_type_size(int type) {
     switch (type) {
@@ -242,7 +256,7 @@ static int  act_kind(int wtype) { return act_kind_of(wtype); }
 int mmq_min_cols_get();
 static int mmq_min_cols() {
     static int v = -1;
-    if (v < 0) { v = 33; if (const char * e = getenv("CLLM_MMQ_MIN_COLS")) { int x = atoi(e); if (x >= 1) v = x; } }
+    if (v < 0) v = opt_int(OPT_CLLM_MMQ_MIN_COLS);
     return v;
 }
 // Columns from which the exact-order GEMM (mmx.hip: one launch, the weights read once, a 64-token tile whatever the count) beats the exact-order mat-vec in chunks of
@@ -250,7 +264,7 @@ static int mmq_min_cols() {
 // wide projections (gate/up) cross at 4-5 columns, the hidden-sized ones (qkv, o, down) at 8-11.  CLLM_MMX_MIN_COLS overrides both.
 static int exact_gemm_min_cols(int64_t nrows) {
     static int v = -2;
-    if (v == -2) { v = -1; if (const char * e = getenv("CLLM_MMX_MIN_COLS")) { int x = atoi(e); if (x >= 1) v = x; } }
+    if (v == -2) v = opt_int(OPT_CLLM_MMX_MIN_COLS);
     return v > 0 ? v : nrows >= 16384 ? 5 : 10;
 }
 // 0: mat-vec in column chunks (mmvq), 1: exact-order GEMM (mmx), 2: the fast / f16 mode's kernels
@@ -262,10 +276,7 @@ static int gemm_path(int64_t M, int64_t nrows) {
 // ---- prefill mode (common.h) ----
 static int g_prefill_mode = -1;
 int prefill_mode() {
-    if (g_prefill_mode < 0) {
-        const char * e = getenv("CLLM_PREFILL");
-        g_prefill_mode = (e && (!strcmp(e, "fast") || !strcmp(e, "f16"))) ? 0 : 1;
-    }
+    if (g_prefill_mode < 0) g_prefill_mode = strcmp(opt_str(OPT_CLLM_PREFILL), "exact") ? 0 : 1;      // fast | f16 (the latter: also dense_f16.hip's prefill_f16_enabled)
     return g_prefill_mode;
 }
 extern "C" int cllm_set_prefill_mode(int mode) {
@@ -278,10 +289,7 @@ extern "C" int cllm_get_prefill_mode(void) { return prefill_mode(); }
 //   CLLM_PREFILL_ATTN=exact | fast overrides what CLLM_PREFILL / cllm_set_prefill_mode say for K.Q / soft_max / V.P; unset (-1): follows prefill_mode()
 static int g_prefill_attn_mode = -2;
 int prefill_attn_mode() {
-    if (g_prefill_attn_mode == -2) {
-        const char * e = getenv("CLLM_PREFILL_ATTN");
-        g_prefill_attn_mode = !e ? -1 : !strcmp(e, "fast") ? 0 : !strcmp(e, "exact") ? 1 : -1;
-    }
+    if (g_prefill_attn_mode == -2) { const char * e = opt_str(OPT_CLLM_PREFILL_ATTN); g_prefill_attn_mode = !strcmp(e, "fast") ? 0 : !strcmp(e, "exact") ? 1 : -1; }
     return g_prefill_attn_mode >= 0 ? g_prefill_attn_mode : prefill_mode();
 }
 extern "C" int cllm_set_prefill_attn_mode(int mode) {

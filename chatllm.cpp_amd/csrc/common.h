@@ -8,6 +8,7 @@
 
 #include "../../include/chatllm_hip.h"
 #include "glibc_math.h"
+#include "options.h"
 
 #define CLLM_WAVE 64
 

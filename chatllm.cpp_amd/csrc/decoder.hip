@@ -179,7 +179,7 @@ extern "C" int cllm_llama_set_tp_fused(cllm_llama * m, void * os) {
     // separate queues -- that only terminates if both ranks' 1024-thread workgroups can be resident at once, i.e. at small shapes.  At hidden sizes whose gather launch fills the
     // GPU by itself the peer's scatter cannot start and every step would end in the bounded wait's time-out: refuse instead.  (Ranks inside one process on one GPU -- the ggml
     // module's virtual ranks -- share a stream and are issued site by site: no such limit.)
-    if (os && cllm_tp_fused_fine_grained(os) == 0 && m->cfg.tp_size > 1 && m->cfg.hidden > 2048 && !getenv("CLLM_TP_FUSED_SAME_DEVICE_ANY_SIZE"))
+    if (os && cllm_tp_fused_fine_grained(os) == 0 && m->cfg.tp_size > 1 && m->cfg.hidden > 2048 && !opt_is_set(OPT_CLLM_TP_FUSED_SAME_DEVICE_ANY_SIZE))
         FAIL(CLLM_E_UNSUPPORTED, "llama_set_tp_fused: ranks of different processes on ONE GPU (coarse-grained receive buffers) cannot co-reside at hidden %d: the fused all-reduce needs distinct GPUs "
                                  "(fine-grained buffers) here; use the collective (cllm_llama_set_tp_oneshot / _set_tp_comm), or CLLM_TP_FUSED_SAME_DEVICE_ANY_SIZE=1 to try anyway", m->cfg.hidden);
     if (m->decode_graph) { (void) hipGraphExecDestroy(m->decode_graph); m->decode_graph = nullptr; }            // (captured with the other form of the all-reduce)
@@ -345,7 +345,7 @@ static int ensure_scores(cllm_llama * m, size_t elems) {
 // prefill (more than 32 columns): MUL_MAT with the SiLU*up quantizer prologue and / or the residual add in the epilogue (cllm_op_mul_mat_ex);
 // CLLM_E_UNSUPPORTED: the caller issues the node sequence
 static int linear_ex(cllm_llama * m, const dweight & w, int64_t K, int64_t N, float * x, int64_t qlen, float * y, int pro, float * resid, const float * norm_w = nullptr, int epi = 0) {
-    if (!is_quant_type(w.type) || getenv("CLLM_NO_PREFILL_FUSE")) return CLLM_E_UNSUPPORTED;
+    if (!is_quant_type(w.type) || opt_is_set(OPT_CLLM_NO_PREFILL_FUSE)) return CLLM_E_UNSUPPORTED;
     cllm_tensor W = T(w.type, w.data, K, N), X = T(CLLM_TYPE_F32, x, pro == 3 ? 2 * K : K, qlen), Y = T(CLLM_TYPE_F32, y, epi ? N / 2 : N, qlen), R = T(CLLM_TYPE_F32, resid, N, qlen);
     cllm_tensor G = T(CLLM_TYPE_F32, (void *) norm_w, K);
     return cllm_op_mul_mat_ex(m->st, &W, &X, &Y, m->wdata, m->wsize, pro, norm_w ? &G : nullptr, m->cfg.rms_eps, epi, resid ? &R : nullptr);
@@ -393,7 +393,7 @@ static int forward_general(cllm_llama * m, int qlen, int n_past) {
             }
         }
         // RoPE + the cache writes: one launch (the same bits as the four below); CLLM_NO_PREFILL_FUSE: the node sequence
-        const bool rope_fused = !getenv("CLLM_NO_PREFILL_FUSE") && qlen > 1;
+        const bool rope_fused = !opt_is_set(OPT_CLLM_NO_PREFILL_FUSE) && qlen > 1;
         if (rope_fused) TRY(launch_rope_kv_store((hipStream_t) st, m->qkv, QKV, m->pos_dev, qlen, (int) nh, (int) nkv, (int) hd, c.rope_mode, c.rope_theta, L.k_cache, L.v_cache, ML));
         else {
         // RoPE in place: k then q  ([hd, heads, qlen] views of the fused buffer)
@@ -512,11 +512,11 @@ extern "C" int cllm_llama_forward(cllm_llama * m, const int32_t * tokens, int ql
 
 // cached positions above which the split attention (attn_long.hip: three launches, every CU) replaces the one-launch kernel (one CU per head).  Both accumulate in
 // ggml_vec_dot_f16's order -- the same bits -- so the threshold is purely a speed matter: the measured crossover is ~400-500 cached positions.
-int attn_long_threshold() { static const int v = getenv("CLLM_ATTN_LONG") ? atoi(getenv("CLLM_ATTN_LONG")) : 512; return v < 64 ? 64 : v; }
+int attn_long_threshold() { static const int v = opt_int(OPT_CLLM_ATTN_LONG); return v; }      // (at least 64: options.def)
 
 // the head of a step: the token's embedding row into m->x and the cos / sin table of its position.  The greedy loop runs it ONCE, in front of its first step: every sampled
 // step ends with k_argmax_final_next, which prepares both for the step after it (CLLM_DECODE_FOLD=0: every step starts with its own head, as before round 5)
-static bool decode_fold() { static const bool v = !(getenv("CLLM_DECODE_FOLD") && atoi(getenv("CLLM_DECODE_FOLD")) == 0); return v; }
+static bool decode_fold() { static const bool v = opt_int(OPT_CLLM_DECODE_FOLD) != 0; return v; }
 static int decode_head(cllm_llama * m) {
     const cllm_llama_config & c = m->cfg;
     const int64_t H = c.hidden, hd = c.head_dim, V = c.vocab;
@@ -686,8 +686,8 @@ extern "C" int cllm_llama_decode_greedy(cllm_llama * m, int32_t first_token, int
     if ((int64_t) n_past + n_steps > m->cfg.max_len) FAIL(CLLM_E_INVALID, "decode_greedy: exceeds max_len");
     if (first_token < 0 || first_token >= m->cfg.vocab) FAIL(CLLM_E_INVALID, "decode_greedy: token id out of range");
     TRY(finalize(m, 1));
-    if (getenv("CLLM_DEBUG")) fprintf(stderr, "[cllm] decode_greedy: fused_ok=%d own_stream=%d use_graph=%d graph=%p\n", (int) m->fused_ok, (int) m->own_stream, (int) m->use_graph, (void *) m->decode_graph);
-    if (m->fused_ok && !getenv("CLLM_NO_FUSED")) {
+    if (opt_is_set(OPT_CLLM_DEBUG)) fprintf(stderr, "[cllm] decode_greedy: fused_ok=%d own_stream=%d use_graph=%d graph=%p\n", (int) m->fused_ok, (int) m->own_stream, (int) m->use_graph, (void *) m->decode_graph);
+    if (m->fused_ok && !opt_is_set(OPT_CLLM_NO_FUSED)) {
         const int32_t init[2] = { first_token, n_past }, zero = 0;
         HIP_TRY(hipMemcpyAsync(m->tokens_dev, &init[0], 4, hipMemcpyHostToDevice, m->st));
         HIP_TRY(hipMemcpyAsync(m->pos_dev, &init[1], 4, hipMemcpyHostToDevice, m->st));

@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(256) k_f32_to_f16(const char * __restrict__ x,
 }
 
 static int g_f16_mode = -1;
-bool prefill_f16_enabled() { if (g_f16_mode < 0) g_f16_mode = getenv("CLLM_PREFILL") && !strcmp(getenv("CLLM_PREFILL"), "f16"); return g_f16_mode != 0; }
+bool prefill_f16_enabled() { if (g_f16_mode < 0) g_f16_mode = !strcmp(opt_str(OPT_CLLM_PREFILL), "f16"); return g_f16_mode != 0; }
 extern "C" __attribute__((visibility("default"))) void cllm_debug_set_prefill_f16(int on) { g_f16_mode = on ? 1 : 0; }      // tests: switch inside one process
 static int g_mmd_tile = -1;
 extern "C" __attribute__((visibility("default"))) void cllm_debug_set_mmd_tile(int tile) { g_mmd_tile = tile; }               // tests / tools: 0 pick, 128, 256
@@ -244,7 +244,7 @@ int launch_dense_f16(hipStream_t st, int wtype, const tview & w, const tview & x
     // the tile: 128 x 128.  256 x 256 (CLLM_MMD_TILE=256 / cllm_debug_set_mmd_tile) is faster per GEMM in isolation where its workgroups fill the CUs evenly
     // (o 254 -> 236 us, down 861 -> 786 us at 4096 tokens) but not in the running prefill: cfg3 113.8 ms with 128 x 128, 114.0 picked per shape, 117.5 ms with
     // 256 x 256 everywhere (tools/prefill_f16_tile_ab.py, one process) -- so it is not picked.
-    if (g_mmd_tile < 0) g_mmd_tile = getenv("CLLM_MMD_TILE") ? atoi(getenv("CLLM_MMD_TILE")) : 0;  // tests / tools: 128 / 256 force
+    if (g_mmd_tile < 0) g_mmd_tile = opt_int(OPT_CLLM_MMD_TILE);  // tests / tools: 128 / 256 force
     const int64_t big_tiles = ((M + 255) / 256) * ((N + 255) / 256);
     const bool big = g_mmd_tile == 256;
 #define GO(T) do { \

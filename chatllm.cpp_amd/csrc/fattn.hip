@@ -430,9 +430,8 @@ __global__ void __launch_bounds__(1024) k_fattn_merge(const fattn_args a) {
 static int g_flash_min = -1;             // -1: not read yet
 int flash_prefill_min_cols() {
     if (g_flash_min < 0) {
-        const char * off = getenv("CLLM_FLASH_PREFILL");
-        const char * e = getenv("CLLM_MMA_MIN_COLS");          // the same threshold as the MFMA mat-muls it replaces (matmul_f.hip): <= 32 columns stay exact
-        g_flash_min = off && atoi(off) == 0 ? 1 << 30 : e ? atoi(e) : 33;
+        // the same threshold as the MFMA mat-muls it replaces (matmul_f.hip): <= 32 columns stay exact
+        g_flash_min = opt_int(OPT_CLLM_FLASH_PREFILL) == 0 ? 1 << 30 : opt_int(OPT_CLLM_MMA_MIN_COLS);
     }
     return g_flash_min;
 }
@@ -497,7 +496,7 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
     a.splits = 1; a.chunk = (int)((n_kv + 63) / 64 * 64); a.part = nullptr; a.n_kv_dev = nullptr;
     if (decode && n_kv > 64) {
         const int tiles = (int)((n_kv + 63) / 64);      // ~2 workgroups per CU, each walking `per` tiles with the next tile's loads in flight
-        static const int div = getenv("CLLM_FA_DIV") ? atoi(getenv("CLLM_FA_DIV")) : 64;
+        static const int div = opt_int(OPT_CLLM_FA_DIV);
         int per = tiles / div; if (per < 1) per = 1; if (per < (tiles + FA_MAX_SPLITS - 1) / FA_MAX_SPLITS) per = (tiles + FA_MAX_SPLITS - 1) / FA_MAX_SPLITS;
         a.chunk = per * 64; a.splits = (tiles + per - 1) / per;
         if (a.splits > 1 && !wdata) { a.splits = 1; a.chunk = (int)((n_kv + 63) / 64 * 64); }      // a caller without scratch (cllm_op_attn_prefill): one workgroup walks the whole cache
@@ -549,7 +548,7 @@ int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * po
                            uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * S, size_t s_bytes, float * att) {
     // opt-in (CLLM_ATTN_LONG_FLASH=1): this form keeps the flash kernel's own summation order (tolerance tier); the default beyond attn_long_threshold() is
     // attn_long.hip, which accumulates in the reference's order
-    static const bool on = getenv("CLLM_ATTN_LONG_FLASH") && atoi(getenv("CLLM_ATTN_LONG_FLASH")) == 1;
+    static const bool on = opt_int(OPT_CLLM_ATTN_LONG_FLASH) == 1;
     if (!on || !rope_cs || (hd != 64 && hd != 128) || nkv <= 0 || nh % nkv || (int64_t) nh / nkv > 32 || ML % 8 || ML > (1 << 30) || ((uintptr_t) S & 15)) return CLLM_E_UNSUPPORTED;
     const size_t q_bytes = ((size_t) nh * hd * 4 + 255) & ~(size_t) 255;
     if (s_bytes <= q_bytes) return CLLM_E_UNSUPPORTED;

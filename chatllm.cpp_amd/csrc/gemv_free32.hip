@@ -8,7 +8,7 @@
 #include "gemv_decode_kernel.h"
 
 static int g_free_order = -1;               // 0 / 1 (anything above 1 is 1: the tier is the only form there is)
-int decode_free_order() { if (g_free_order < 0) g_free_order = getenv("CLLM_DECODE_FREE_ORDER") && atoi(getenv("CLLM_DECODE_FREE_ORDER")) > 0 ? 1 : 0; return g_free_order; }
+int decode_free_order() { if (g_free_order < 0) g_free_order = opt_int(OPT_CLLM_DECODE_FREE_ORDER); return g_free_order; }
 extern "C" CLLM_API int cllm_set_decode_free_order(int on) { g_free_order = on > 0 ? 1 : 0; return CLLM_OK; }
 extern "C" CLLM_API int cllm_get_decode_free_order(void) { return decode_free_order(); }
 

@@ -240,7 +240,7 @@ static int gemv_rows_go(hipStream_t st, const void * W, int64_t K, int64_t nrows
                         const float * bias, const float * resid, int * grid_out) {
     // 0: off; 1 (default): only where it measured faster than k_gemv_dec -- many rows per CU (lm_head: 78 -> 62 us; gate/up and the small
     // projections are a draw or slower: one unit per wave leaves no steady state); 2: everything it can take; 8 / 4: that too, with RPW forced
-    static const int mode = getenv("CLLM_GEMV_ROWS") ? atoi(getenv("CLLM_GEMV_ROWS")) : 1;
+    static const int mode = opt_int(OPT_CLLM_GEMV_ROWS);
     if (!mode || K % 256 || pro < 1 || pro > 4 || nrows <= 0 || (uint64_t) nrows * (uint64_t)(K / 256 * 144) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
     if (K > ((pro == 2 || pro == 4) ? 32768 : 16384)) return CLLM_E_UNSUPPORTED;
     if (epi == 1 && (pro != 1 || bias || resid)) return CLLM_E_UNSUPPORTED;

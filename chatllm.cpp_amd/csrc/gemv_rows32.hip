@@ -222,7 +222,7 @@ extern "C" __attribute__((visibility("default"))) void cllm_debug_set_gemv_rows3
 // K % 32 == 0, rows whole dwords (Q4_0 / Q8_0: K % 64 == 0), nrows % RPW == 0; CLLM_E_UNSUPPORTED: k_gemv_dec takes the launch
 int launch_gemv_rows32(hipStream_t st, int wtype, const void * W, int64_t K, int64_t nrows, int pro, const float * px, const float * pw, float eps, int epi, float * dst,
                        const float * bias, const float * resid) {
-    if (g_rows32_mode < 0) g_rows32_mode = getenv("CLLM_GEMV_ROWS32") ? atoi(getenv("CLLM_GEMV_ROWS32")) : 1;      // 0: off, 2 / 4 / 8: that many rows per wave where the shape allows
+    if (g_rows32_mode < 0) g_rows32_mode = opt_int(OPT_CLLM_GEMV_ROWS32);      // 0: off, 2 / 4 / 8: that many rows per wave where the shape allows
     const int mode = g_rows32_mode;
     if (!mode || (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0)) return CLLM_E_UNSUPPORTED;
     const int bs = wtype == CLLM_TYPE_Q8_0 ? 34 : wtype == CLLM_TYPE_Q4_1 ? 20 : 18;

@@ -383,7 +383,7 @@ int kernel_error_word(unsigned ** dev_ptr) {
 // K % 32 == 0, rows whole dwords, nrows % 8 == 0, one unit (8 rows) per team; CLLM_E_UNSUPPORTED: the caller's other kernels take the launch
 int launch_gemv_team32(hipStream_t st, int wtype, const void * W, int64_t K, int64_t nrows, int pro, const float * px, const float * pw, float eps, int epi, float * dst,
                        const float * bias, const float * resid) {
-    if (g_team32_mode < 0) g_team32_mode = getenv("CLLM_GEMV_TEAM32") ? atoi(getenv("CLLM_GEMV_TEAM32")) : 1;
+    if (g_team32_mode < 0) g_team32_mode = opt_int(OPT_CLLM_GEMV_TEAM32);
     const int mode = g_team32_mode;
     if (!mode || epi != 0 || (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0)) return CLLM_E_UNSUPPORTED;
     const int bs = wtype == CLLM_TYPE_Q8_0 ? 34 : wtype == CLLM_TYPE_Q4_1 ? 20 : 18;

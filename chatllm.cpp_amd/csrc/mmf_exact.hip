@@ -368,7 +368,7 @@ int launch_mmf_exact(hipStream_t st, const tview & w, const tview & x, const tvi
     const int64_t K = w.ne[0], N = w.ne[1], M = x.ne[1], Z = x.ne[2] * x.ne[3];
     if (K <= 0 || N <= 0 || M <= 0 || Z <= 0 || Z > 65535) return CLLM_E_UNSUPPORTED;
     mmfx_args a; a.w = w; a.x = x; a.d = d; a.causal = causal; a.n_past = n_past; a.x_f16 = x_f16 ? 1 : 0;
-    static const int zf_mode = getenv("CLLM_MMF_ZFIRST") ? atoi(getenv("CLLM_MMF_ZFIRST")) : 1;      // (tools: 0 = the heads on grid z as before)
+    static const int zf_mode = opt_int(OPT_CLLM_MMF_ZFIRST);      // (tools: 0 = the heads on grid z as before)
     auto grid = [&](int64_t tm, int64_t tn) {                       // column tiles x row tiles x batch, in the order a.zfirst says
         a.zfirst = (zf_mode && causal != 0 && tm <= 65535) ? 1 : 0;
         return a.zfirst ? dim3((unsigned) Z, (unsigned) tn, (unsigned) tm) : dim3((unsigned) tm, (unsigned) tn, (unsigned) Z);
@@ -380,7 +380,7 @@ int launch_mmf_exact(hipStream_t st, const tview & w, const tview & x, const tvi
         if ((N + 63) / 64 > 65535) return CLLM_E_UNSUPPORTED;
         // the narrow tile (64 rows x 32 columns, three workgroups per CU) for both contractions of the prompt's attention: measured at cfg3 (profiles/r04_mmf_exact_tile.txt)
         // 406.3 ms against 414.6-416.0 with the square tile and 413.5 with the narrow one on K.Q only -- a third resident workgroup covers the other two's stage loads
-        static const int kq_mode = getenv("CLLM_MMF_KQ") ? atoi(getenv("CLLM_MMF_KQ")) : 1;       // (tools: 0 = the LDS-staged tiles for the single-stage shapes too)
+        static const int kq_mode = opt_int(OPT_CLLM_MMF_KQ);       // (tools: 0 = the LDS-staged tiles for the single-stage shapes too)
         const bool al16 = ((((uintptr_t) w.data) | (uintptr_t) w.nb[1] | (uintptr_t) w.nb[2] | (uintptr_t) w.nb[3] | ((uintptr_t) x.data) | (uintptr_t) x.nb[1] | (uintptr_t) x.nb[2] | (uintptr_t) x.nb[3]) & 15) == 0;
         if (kq_mode && al16 && K <= MMFX_KC && !x_f16 && causal != 2 && M > 32 && N >= 256 && N < (1 << 30) && (M + 63) / 64 <= 65535) {      // a prompt's K.Q: waves walk the rows of their 16 columns
             const dim3 gr = grid((M + 63) / 64, 1);
@@ -388,7 +388,7 @@ int launch_mmf_exact(hipStream_t st, const tview & w, const tview & x, const tvi
             LAUNCH_CHECK();
             return CLLM_OK;
         }
-        static const int force_pm = getenv("CLLM_MMF_PM") ? atoi(getenv("CLLM_MMF_PM")) : 0;      // (tools: 2 forces the 64 x 64 tile)
+        static const int force_pm = opt_int(OPT_CLLM_MMF_PM);      // (tools: 2 forces the 64 x 64 tile)
         const int pm = force_pm == 2 ? 2 : 1;
         if (pm == 1) { const dim3 gr = grid((M + 31) / 32, (N + 63) / 64); hipLaunchKernelGGL((k_mmf_exact<false, 1>), gr, dim3(256), 0, st, a); }
         else         { const dim3 gr = grid((M + 63) / 64, (N + 63) / 64); hipLaunchKernelGGL((k_mmf_exact<false, 2>), gr, dim3(256), 0, st, a); }

@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
 }
 
 int launch_mmq(hipStream_t st, int wtype, const tview & w, const void * act, size_t act_stride, const tview & x, const tview & d, const float * resid, int64_t ldr, int epi) {
-    if (getenv("CLLM_NO_MMQ")) return CLLM_E_UNSUPPORTED;
+    if (opt_is_set(OPT_CLLM_NO_MMQ)) return CLLM_E_UNSUPPORTED;
     if (d.nb[1] % 4) FAIL(CLLM_E_INVALID, "mmq: dst stride");
     mmq_args a;
     a.W = w.data; a.nb01 = w.nb[1]; a.N = w.ne[1]; a.K = w.ne[0];

@@ -280,9 +280,8 @@ static void mmvq_tunables() {
     static bool done = false;
     if (done) return;
     done = true;
-    if (const char * e = getenv("CLLM_MMVQ_WG"))  { int v = atoi(e); if (v == 64 || v == 128 || v == 256 || v == 512) g_mmvq_wg = v; }
-    if (const char * e = getenv("CLLM_MMVQ_OCC")) { int v = atoi(e); if (v >= 1 && v <= 32) g_mmvq_wgs_per_cu = v; }
-    if (const char * e = getenv("CLLM_MMVQ_WG"))   { int v = atoi(e); if (v == 1024) g_mmvq_wg = v; }
+    g_mmvq_wg = opt_int(OPT_CLLM_MMVQ_WG);
+    g_mmvq_wgs_per_cu = opt_int(OPT_CLLM_MMVQ_OCC);
 }
 
 template <typename KernelT>

@@ -427,7 +427,7 @@ int launch_mmx(hipStream_t st, int wtype, const tview & w, const void * act, siz
         const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN))); \
         if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmx<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL(k_mmx<T>, grid, dim3(256), LDS, st, a); } while (0)
-    static const bool dbg = getenv("CLLM_DEBUG") != nullptr;
+    static const bool dbg = opt_is_set(OPT_CLLM_DEBUG);
     if (dbg) {
         int nb = 0;
         (void) hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *) k_mmx<CLLM_TYPE_Q4_0>, 256, mmx_lds<CLLM_TYPE_Q4_0>());

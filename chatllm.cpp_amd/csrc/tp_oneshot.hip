@@ -102,8 +102,7 @@ int cllm_tp_oneshot_create(int rank, int nranks, size_t max_n, void ** out, void
     o->fine_grained = e == hipSuccess;
     if (e != hipSuccess) {
         (void) hipGetLastError();
-        const char * same = getenv("CLLM_TP_ONESHOT_SAME_DEVICE");
-        if (!same || strcmp(same, "1")) { delete o; FAIL(CLLM_E_UNSUPPORTED, "tp_oneshot_create: fine-grained IPC memory is not available (%s); the coarse-grained fallback is only valid when all ranks share one GPU (CLLM_TP_ONESHOT_SAME_DEVICE=1)", hipGetErrorString(e)); }
+        if (strcmp(opt_str(OPT_CLLM_TP_ONESHOT_SAME_DEVICE), "1")) { delete o; FAIL(CLLM_E_UNSUPPORTED, "tp_oneshot_create: fine-grained IPC memory is not available (%s); the coarse-grained fallback is only valid when all ranks share one GPU (CLLM_TP_ONESHOT_SAME_DEVICE=1)", hipGetErrorString(e)); }
         HIP_TRY(hipMalloc((void **) &o->local, bytes));
         HIP_TRY(hipIpcGetMemHandle(&h, o->local));
     }
@@ -204,8 +203,7 @@ int cllm_tp_fused_create(int rank, int nranks, int n_sites, size_t max_n, void *
     o->fine_grained = e == hipSuccess;
     if (e != hipSuccess) {
         (void) hipGetLastError();
-        const char * same = getenv("CLLM_TP_ONESHOT_SAME_DEVICE");
-        if (!same || strcmp(same, "1")) { delete o; FAIL(CLLM_E_UNSUPPORTED, "tp_fused_create: fine-grained IPC memory is not available (%s); the coarse-grained fallback is only valid when all ranks share one GPU (CLLM_TP_ONESHOT_SAME_DEVICE=1)", hipGetErrorString(e)); }
+        if (strcmp(opt_str(OPT_CLLM_TP_ONESHOT_SAME_DEVICE), "1")) { delete o; FAIL(CLLM_E_UNSUPPORTED, "tp_fused_create: fine-grained IPC memory is not available (%s); the coarse-grained fallback is only valid when all ranks share one GPU (CLLM_TP_ONESHOT_SAME_DEVICE=1)", hipGetErrorString(e)); }
         HIP_TRY(hipMalloc((void **) &o->local, bytes));
         HIP_TRY(hipIpcGetMemHandle(&h, o->local));
     }

@@ -65,11 +65,31 @@ struct wall_stats {
     double host_us = 0, plan_us = 0, issue_us = 0, sync_us = 0, set_us = 0, get_us = 0, alloc_us = 0; long graphs = 0, calls = 0, sets = 0, gets = 0, allocs = 0, syncs = 0;
     static double us(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
 } g_ws;
-const bool g_stats = getenv("CLLM_HIP_STATS") != nullptr;
+// every CLLM_HIP_* switch (csrc/options.def has their meaning): read ONCE through the library's table by ggml_backend_init, before the devices are registered;
+// everything after that reads plain fields
+struct host_options {
+    bool stats = false, trace = false, sig_debug = false, tp_debug = false, ahead_debug = false, ahead_timing = false, ahead_sync = false, ahead_late = false;
+    bool sync_load = false, force_stage = false, no_fuse = false, no_prefill_fuse = false, no_moe_down_fuse = false;
+    bool pack = true, graph = true, moe_fold = true, ahead = true, ahead_chain = true, ahead_one = true, tp_streams = false, tp_head = true, tp_graph = true;
+    int fuse_attn = 2, virtual_devices = 0, tp = 0;
+    double pack_gb = -1.0;
+    void read() {
+        stats = cllm_option_is_set("CLLM_HIP_STATS"); trace = cllm_option_is_set("CLLM_HIP_TRACE"); sig_debug = cllm_option_is_set("CLLM_HIP_SIG_DEBUG");
+        tp_debug = cllm_option_is_set("CLLM_HIP_TP_DEBUG"); ahead_debug = cllm_option_is_set("CLLM_HIP_AHEAD_DEBUG"); ahead_timing = cllm_option_is_set("CLLM_HIP_AHEAD_TIMING");
+        ahead_sync = cllm_option_is_set("CLLM_HIP_AHEAD_SYNC"); ahead_late = cllm_option_is_set("CLLM_HIP_AHEAD_LATE"); sync_load = cllm_option_is_set("CLLM_HIP_SYNC_LOAD");
+        force_stage = cllm_option_is_set("CLLM_HIP_FORCE_STAGE"); no_fuse = cllm_option_is_set("CLLM_HIP_NO_FUSE"); no_prefill_fuse = cllm_option_is_set("CLLM_HIP_NO_PREFILL_FUSE");
+        no_moe_down_fuse = cllm_option_is_set("CLLM_HIP_NO_MOE_DOWN_FUSE");
+        pack = cllm_option_int("CLLM_HIP_PACK") != 0; graph = cllm_option_int("CLLM_HIP_GRAPH") != 0; moe_fold = cllm_option_int("CLLM_HIP_MOE_FOLD") != 0;
+        ahead = cllm_option_int("CLLM_HIP_AHEAD") != 0; ahead_chain = cllm_option_int("CLLM_HIP_AHEAD_CHAIN") != 0; ahead_one = cllm_option_int("CLLM_HIP_AHEAD_ONE") != 0;
+        tp_streams = cllm_option_int("CLLM_HIP_TP_STREAMS") != 0; tp_head = cllm_option_int("CLLM_HIP_TP_HEAD") != 0; tp_graph = cllm_option_int("CLLM_HIP_TP_GRAPH") != 0;
+        fuse_attn = cllm_option_int("CLLM_HIP_FUSE_ATTN"); virtual_devices = cllm_option_int("CLLM_HIP_VIRTUAL_DEVICES"); tp = cllm_option_int("CLLM_HIP_TP");
+        pack_gb = cllm_option_real("CLLM_HIP_PACK_GB");
+    }
+} g_opt;
 struct ws_scope {        // time inside one of our entry points goes to `slot`, the time since the previous one to host_us
     double & slot; wall_stats::clk::time_point t0;
-    explicit ws_scope(double & s) : slot(s), t0(wall_stats::clk::now()) { if (g_stats) g_ws.host_us += wall_stats::us(g_ws.last_exit, t0); }
-    ~ws_scope() { if (g_stats) { const auto t1 = wall_stats::clk::now(); slot += wall_stats::us(t0, t1); g_ws.last_exit = t1; } }
+    explicit ws_scope(double & s) : slot(s), t0(wall_stats::clk::now()) { if (g_opt.stats) g_ws.host_us += wall_stats::us(g_ws.last_exit, t0); }
+    ~ws_scope() { if (g_opt.stats) { const auto t1 = wall_stats::clk::now(); slot += wall_stats::us(t0, t1); g_ws.last_exit = t1; } }
 };
 
 std::atomic<uint64_t> g_tp_kv_epoch{1};          // tensor parallel (tp_graph_compute): bumped by everything that may have changed the host's KV caches behind the ranks' shards
@@ -168,8 +188,7 @@ bool ring_set(set_ring & r, int device, void * dst, const void * data, size_t si
 }
 // a host buffer of any size into device memory: through the bulk ring (asynchronous), else a blocking copy
 bool upload(int device, void * dst, const void * data, size_t size) {
-    static const bool sync_loader = getenv("CLLM_HIP_SYNC_LOAD") != nullptr;       // (A/B: the blocking path)
-    if (!sync_loader && ring_set(g_bulk, device, dst, data, size)) return true;
+    if (!g_opt.sync_load && ring_set(g_bulk, device, dst, data, size)) return true;
     return cllm_memcpy_h2d(dst, data, size, nullptr) == CLLM_OK && cllm_stream_sync(nullptr) == CLLM_OK;
 }
 
@@ -230,9 +249,8 @@ void buf_get(ggml_backend_buffer_t b, const ggml_tensor * t, void * data, size_t
     const char * src = (const char *) t->data + off;
     // the host reads the logits: the next step is started FIRST (it snapshots the graph's outputs on its stream, then runs), and the 513 KB copy to the host below is
     // served from that snapshot while the step already computes -- started after the copy, the GPU idled for the copy's ~70 us of every token
-    static const bool ahead_late = getenv("CLLM_HIP_AHEAD_LATE") != nullptr;       // (A/B switch: round 3's order)
     const bool is_logits_read = ac && ac->ahead.armed && !ac->ahead.inflight && (const void *) t->data == ac->ahead.logits_ptr && off == 0 && size == ac->ahead.logits_bytes;
-    if (is_logits_read && !ahead_late) ahead_launch(ac);
+    if (is_logits_read && !g_opt.ahead_late) ahead_launch(ac);      // (CLLM_HIP_AHEAD_LATE, A/B: round 3's order)
     if (ac && (ac->ahead.inflight || (is_logits_read && ac->ahead.snap_ready))) {
         bool served = false;
         if (ac->ahead.inflight) ahead_finish_event(ac);      // (a host that reads without synchronize(): the snapshot must be complete)
@@ -242,7 +260,7 @@ void buf_get(ggml_backend_buffer_t b, const ggml_tensor * t, void * data, size_t
         ac->ahead.snap_ready = false;
     }
     buf_get_impl(b, src, t->name, data, size);
-    if (is_logits_read && ahead_late && ac->ahead.armed && !ac->ahead.inflight) ahead_launch(ac);
+    if (is_logits_read && g_opt.ahead_late && ac->ahead.armed && !ac->ahead.inflight) ahead_launch(ac);
 }
 void buf_get_impl(ggml_backend_buffer_t b, const char * src, const char * name, void * data, size_t size) {
     std::lock_guard<std::mutex> lock(g_stage_mutex);            // one staging area (accessory models may read from other threads)
@@ -313,8 +331,7 @@ void packs_forget(uint64_t uid) {
 bool ours(const ggml_tensor * t) { return t && t->buffer && t->buffer->iface.free_buffer == buf_free && !t->view_src; }
 // the packed copy of n (2 or 3) same-type, same-row-length weight matrices, or nullptr (not ours / over budget / allocation failed)
 void * get_pack(int device, void * stream, const ggml_tensor * const * w, int n, bool interleave, bool flat = false) {      // flat: byte blobs (bias vectors)
-    static const bool off = getenv("CLLM_HIP_PACK") && atoi(getenv("CLLM_HIP_PACK")) == 0;
-    if (off) return nullptr;
+    if (!g_opt.pack) return nullptr;
     for (int i = 0; i < n; i++) if (!ours(w[i]) || ((const hip_buffer_ctx *) w[i]->buffer->context)->device != device) return nullptr;
     std::lock_guard<std::mutex> lock(g_pack_mutex);
     pack_entry & e = g_packs[w[0]->data];
@@ -335,7 +352,7 @@ void * get_pack(int device, void * stream, const ggml_tensor * const * w, int n,
     }
     size_t mfree = 0, mtotal = 0;
     cllm_device_info(device, nullptr, 0, &mfree, &mtotal, nullptr);
-    static const double cap_gb = getenv("CLLM_HIP_PACK_GB") ? atof(getenv("CLLM_HIP_PACK_GB")) : -1.0;
+    const double cap_gb = g_opt.pack_gb;
     const size_t cap = cap_gb >= 0 ? (size_t)(cap_gb * 1e9) : mtotal / 4;
     if (g_pack_bytes + bytes > cap || mfree < bytes + mtotal / 10) return nullptr;
     void * p = nullptr;
@@ -598,7 +615,7 @@ struct node_index {                 // ggml_tensor * -> position in the graph (o
 
 void plan_attention(ggml_cgraph * g, fuse_plan & P, const std::vector<int> & local, const std::vector<int> & writer,
                     const user_lists & users, const node_index & find) {
-    static const int max_level = getenv("CLLM_HIP_FUSE_ATTN") ? atoi(getenv("CLLM_HIP_FUSE_ATTN")) : 2;
+    const int max_level = g_opt.fuse_attn;
     if (max_level <= 0) return;
     const int n = ggml_graph_n_nodes(g);
     auto node = [&](int i) { return ggml_graph_node(g, i); };
@@ -630,7 +647,7 @@ void plan_attention(ggml_cgraph * g, fuse_plan & P, const std::vector<int> & loc
                 vv->type == GGML_TYPE_F16 && vv->ne[0] == n_kv && vv->ne[1] == hd && vv->ne[2] == nkv && vv->ne[3] == 1 && vv->nb[0] == 2 && al16(vv) && (int64_t)(vv->nb[1] / 2) >= n_kv &&
                 ggml_is_contiguous(kqv) && sm->src[0]->src[0] == scn) {
                 fused_fa F; F.ikq = ikq; F.n_past = n_past; memcpy(&F.scale, scn->op_params, 4);
-                static const bool force_stage = getenv("CLLM_HIP_FORCE_STAGE") != nullptr;
+                const bool force_stage = g_opt.force_stage;
                 size_t qext = 0;                            // the bytes the (permuted) q view spans
                 for (int k = 0; k < 4; k++) qext += (size_t)(qp->ne[k] - 1) * qp->nb[k];
                 F.bytes = ggml_nbytes(kqv);
@@ -728,8 +745,7 @@ void plan_attention(ggml_cgraph * g, fuse_plan & P, const std::vector<int> & loc
 fuse_plan make_plan(ggml_cgraph * g) {
     const int n = ggml_graph_n_nodes(g);
     fuse_plan P; P.skip.assign(n, 0); P.mv.assign(n, -1); P.sm_src.assign(n, -1); P.attn.assign(n, -1); P.alt.assign(n, ALT_NONE); P.moe.assign(n, -1); P.pf.assign(n, -1);
-    static const bool off = getenv("CLLM_HIP_NO_FUSE") != nullptr;
-    if (off || n < 8) return P;
+    if (g_opt.no_fuse || n < 8) return P;
     std::vector<int> local(n, 0), writer(n, -1);        // writer[i]: entry of mvs whose launch produces node i
     static thread_local node_index find;
     static thread_local user_lists users;
@@ -817,7 +833,7 @@ fuse_plan make_plan(ggml_cgraph * g) {
         }
     }
     // ---- prefill: the same three patterns around a many-column quantized MUL_MAT (cllm_op_mul_mat_ex; the runner's prefill has them too)
-    static const bool no_pf = getenv("CLLM_HIP_NO_PREFILL_FUSE") != nullptr;
+    const bool no_pf = g_opt.no_prefill_fuse;
     static const int pf_min = cllm_mul_mat_ex_min_cols();
     auto pf_ok = [&](const ggml_tensor * mm) {
         if (mm->op != GGML_OP_MUL_MAT) return false;
@@ -927,7 +943,7 @@ fuse_plan make_plan(ggml_cgraph * g) {
     // them; `up` of SILU->MUL(up)->MUL_MAT, the normalised activation ...) may already be free when dst is placed -- so dst can land on an
     // input.  Such launches write to module scratch and are copied into place afterwards (graph_compute); an in-place residual (dst == resid)
     // is fine: every element is read and written by the same lane.
-    static const bool force_stage = getenv("CLLM_HIP_FORCE_STAGE") != nullptr;      // (tests: take the staged path everywhere)
+    const bool force_stage = g_opt.force_stage;      // (tests: take the staged path everywhere)
     for (fused_mv & f : P.mvs) {
         if (f.node < 0 || !f.dst) continue;
         const ggml_tensor * w = ggml_graph_node(g, f.node)->src[0];
@@ -1079,8 +1095,7 @@ fuse_plan make_plan(ggml_cgraph * g) {
         {   // the experts are the down projection's MUL_MAT_ID of one token over two slots: mat-vecs and tail in one launch (cllm_op_mul_mat_id_combine)
             const int ia = find(a);
             const ggml_tensor * out = ggml_graph_node(g, fin), * w = a->src[0], * x = a->src[1];
-            static const bool no_down = getenv("CLLM_HIP_NO_MOE_DOWN_FUSE") != nullptr;
-            if (!no_down && a->op == GGML_OP_MUL_MAT_ID && ia >= 0 && !P.skip[ia] && only_local(ia, 1) && k == 2 && T == 1 && a->src[2] == ids && is_q(w->type) && w->ne[3] == 1 &&
+            if (!g_opt.no_moe_down_fuse && a->op == GGML_OP_MUL_MAT_ID && ia >= 0 && !P.skip[ia] && only_local(ia, 1) && k == 2 && T == 1 && a->src[2] == ids && is_q(w->type) && w->ne[3] == 1 &&
                 w->nb[1] == ggml_row_size(w->type, w->ne[0]) && w->nb[2] % 16 == 0 && ((uintptr_t) w->data & 15) == 0 && w->ne[0] <= 32768 && (uint64_t) w->ne[1] * w->nb[1] < (1ull << 32) &&
                 x->type == GGML_TYPE_F32 && x->ne[1] == 2 && x->ne[2] == 1 && x->ne[3] == 1 && x->nb[0] == 4 && x->nb[1] % 16 == 0 && ((uintptr_t) x->data & 15) == 0 &&
                 probs->ne[0] == w->ne[2] && ggml_nelements(probs) == probs->ne[0] &&
@@ -1179,7 +1194,7 @@ void ahead_launch(hip_backend_ctx * c, bool chained) {
     // CLLM_HIP_AHEAD_TIMING=1 (diagnosis): per step, on the GPU's clock -- the captured step alone, what stands in front of it (table copy, prep launch, event), and the token
     // period; a ring of four event triples, read two launches later (the host has synchronized on a later event by then, also with the chain on)
     static void * t_p[4] = {}, * t_g0[4] = {}, * t_g1[4] = {}; static long t_n = 0; static double acc_graph = 0, acc_prep = 0, acc_period = 0; static long acc_n = 0;
-    static const bool timing = getenv("CLLM_HIP_AHEAD_TIMING") != nullptr;
+    const bool timing = g_opt.ahead_timing;
     const int t_k = (int)(t_n & 3);
     if (timing) {
         if (!t_p[0]) for (int i = 0; i < 4; i++) { cllm_event_create(&t_p[i]); cllm_event_create(&t_g0[i]); cllm_event_create(&t_g1[i]); }
@@ -1193,8 +1208,7 @@ void ahead_launch(hip_backend_ctx * c, bool chained) {
     }
     if (n_rec && cllm_memcpy_h2d(A.table_dev, A.tab_host, (size_t) n_rec * 16, st) != CLLM_OK) return;      // queued on the step's stream from page-locked memory; done before the event below
     // the snapshot of the outputs, the arg-max and the scalar updates: ONE launch (cllm_op_snapshot_argmax_set; CLLM_HIP_AHEAD_ONE=0: round 5's copies + two launches)
-    static const bool one_launch = !getenv("CLLM_HIP_AHEAD_ONE") || atoi(getenv("CLLM_HIP_AHEAD_ONE")) != 0;
-    bool fused_prep = one_launch && A.outs.size() <= 16;
+    bool fused_prep = g_opt.ahead_one && A.outs.size() <= 16;
     for (const auto & o : A.outs) fused_prep = fused_prep && o.bytes % 4 == 0;
     if (fused_prep) {
         bool same = A.rng_cur.size() == A.outs.size();
@@ -1217,8 +1231,7 @@ void ahead_launch(hip_backend_ctx * c, bool chained) {
     if (timing) cllm_event_record(t_g0[t_k], st);
     if ((A.tp ? tp_ahead_replay(c) : cllm_graph_launch(c->graph_exec, st)) != CLLM_OK) { fail_behind_the_snapshot(); return; }
     if (timing) { cllm_event_record(t_g1[t_k], st); t_n++; }
-    static const bool ahead_sync = getenv("CLLM_HIP_AHEAD_SYNC") != nullptr;       // (debugging: run the step ahead to completion before returning)
-    if (ahead_sync) cllm_stream_sync(st);
+    if (g_opt.ahead_sync) cllm_stream_sync(st);       // (debugging: run the step ahead to completion before returning)
     A.inflight = true; A.launched++; A.chained = chained; A.ev_pending = true;
     // not chained: the snapshot and the scalars are in place before the host goes on (its own writes of the same scalars come later); the device then holds the predicted
     // scalars: the host-side mirror is brought in step (the host will write the same values again).  Chained: synchronize() does both.
@@ -1236,8 +1249,7 @@ int ahead_resolve(hip_backend_ctx * c, bool sig_equal, const std::vector<hip_bac
     for (size_t k = 0; ok && k < cur_sets.size(); k++)
         ok = cur_sets[k].ptr == A.pred[k].ptr && cur_sets[k].val == (A.pred[k].ptr == A.ids_ptr ? A.tok_host[0] : A.pred[k].val);
     if (ok) { A.hits++; A.misses = 0; return 1; }
-    static const bool adbg = getenv("CLLM_HIP_AHEAD_DEBUG") != nullptr;
-    if (adbg) {
+    if (g_opt.ahead_debug) {
         HIPB_LOG("ahead: MISS sig_equal=%d sets %zu predicted %zu", (int) sig_equal, cur_sets.size(), A.pred.size());
         for (size_t k = 0; k < cur_sets.size() && k < A.pred.size(); k++) {
             const int32_t want = A.pred[k].ptr == A.ids_ptr ? A.tok_host[0] : A.pred[k].val;
@@ -1325,8 +1337,7 @@ int tp_ensure_group(hip_backend_ctx * c, int n_sites, size_t max_n) {
             R.gpu = (c->device + k) % (phys > 0 ? phys : 1);
             // CLLM_HIP_TP_STREAMS=1 (tests): ranks that share rank 0's GPU get streams of their own as well -- the event / cross-stream path of distinct GPUs on a one-GPU box.
             // Only for shapes whose launches can all be resident at once (a gather polls for scatters of other streams): the test shapes; bounded waits otherwise report a time-out.
-            static const bool force_streams = getenv("CLLM_HIP_TP_STREAMS") && atoi(getenv("CLLM_HIP_TP_STREAMS")) != 0;
-            if (R.gpu == c->device && !(force_streams && k > 0)) R.stream = c->stream;
+            if (R.gpu == c->device && !(g_opt.tp_streams && k > 0)) R.stream = c->stream;
             else {
                 cllm_set_device(R.gpu);
                 if (int rc = cllm_stream_create(&R.stream)) { cllm_set_device(c->device); return rc; }
@@ -1423,12 +1434,11 @@ int ahead_resolve(hip_backend_ctx * c, bool sig_equal, const std::vector<hip_bac
 ggml_status tp_graph_compute(hip_backend_ctx * c, ggml_cgraph * g, fuse_plan & P, const std::vector<hip_backend_ctx::scalar_set> & cur_sets, bool * replayed_out) {
     auto & T = g_tp;
     tp_desc D;
-    static const bool tp_dbg = getenv("CLLM_HIP_TP_DEBUG") != nullptr;
+    const bool tp_dbg = g_opt.tp_debug;
 #define TP_NO() (tp_dbg ? (fprintf(stderr, "[ggml-hip] tensor parallel: decode step not taken (ggml-hip.cpp:%d): un-sharded on rank 0\n", __LINE__), GGML_STATUS_ABORTED) : GGML_STATUS_ABORTED)
     if (T.broken) return GGML_STATUS_ABORTED;
     if (!tp_extract(g, P, D)) {
-        static const bool dbg = getenv("CLLM_HIP_TP_DEBUG") != nullptr;
-        if (dbg) HIPB_LOG("tensor parallel: a %d-node graph is not the decode step (%zu layers matched, embed %d, head %d/%d/%d): un-sharded on rank 0", ggml_graph_n_nodes(g), D.layers.size(), D.embed, D.head, D.head_norm, D.head_mm);
+        if (tp_dbg) HIPB_LOG("tensor parallel: a %d-node graph is not the decode step (%zu layers matched, embed %d, head %d/%d/%d): un-sharded on rank 0", ggml_graph_n_nodes(g), D.layers.size(), D.embed, D.head, D.head_norm, D.head_mm);
         return GGML_STATUS_ABORTED;
     }
     auto node = [&](int i) { return ggml_graph_node(g, i); };
@@ -1642,7 +1652,7 @@ ggml_status tp_graph_compute(hip_backend_ctx * c, ggml_cgraph * g, fuse_plan & P
     // ---- the head's operands.  Sharded by ROWS of the lm_head (default; CLLM_HIP_TP_HEAD=0: all of it on rank 0): every rank folds the last all-reduce into its own residual
     //      stream and writes its logit rows straight into the host's logits tensor in rank 0's memory (a peer store from another GPU); a row's arithmetic does not change, so the
     //      logits are the bits rank 0 alone would have produced from the same residual stream.  chatllm keeps the normalised hidden state as a graph OUTPUT: rank 0 also runs that node.
-    static const bool shard_head = !getenv("CLLM_HIP_TP_HEAD") || atoi(getenv("CLLM_HIP_TP_HEAD")) != 0;
+    const bool shard_head = g_opt.tp_head;
     const fused_mv * fh = D.head >= 0 ? &P.mvs[D.head] : nullptr;
     ggml_tensor * hn = D.head >= 0 ? nullptr : node(D.head_norm), * hm = D.head >= 0 ? nullptr : node(D.head_mm);
     const float * norm_w = fh ? fh->pw : (const float *) hn->src[1]->data;
@@ -1754,7 +1764,7 @@ ggml_status tp_graph_compute(hip_backend_ctx * c, ggml_cgraph * g, fuse_plan & P
     };
     // ---- launch-list replay per stream (as be_graph_compute does for one stream): everything a launch depends on goes into a signature; the second identical step is captured,
     //      one graph per distinct stream (ranks on distinct GPUs: one each; virtual ranks: one for all), and replayed from then on.  CLLM_HIP_TP_GRAPH=0: every launch issued ----
-    static const bool tp_graph = !getenv("CLLM_HIP_TP_GRAPH") || atoi(getenv("CLLM_HIP_TP_GRAPH")) != 0;
+    const bool tp_graph = g_opt.tp_graph;
     std::vector<uint64_t> sig;
     {
         auto put = [&](const void * p) { sig.push_back((uint64_t)(uintptr_t) p); };
@@ -1837,7 +1847,7 @@ ggml_status tp_graph_compute(hip_backend_ctx * c, ggml_cgraph * g, fuse_plan & P
 #undef TP_NO
     cllm_set_device(c->device);
     T.steps++; T.last_tp = true;
-    if (g_stats) HIPB_LOG("HIP0 graph_compute: %d nodes -> tensor parallel over %d ranks: %d launches per rank (%d layers x 5 + head%s)%s, all-reduce fused into the mat-vecs", ggml_graph_n_nodes(g), N, 5 * L + 6, L,
+    if (g_opt.stats) HIPB_LOG("HIP0 graph_compute: %d nodes -> tensor parallel over %d ranks: %d launches per rank (%d layers x 5 + head%s)%s, all-reduce fused into the mat-vecs", ggml_graph_n_nodes(g), N, 5 * L + 6, L,
                           sharded ? ", lm_head rows sharded" : "", ahead_hit ? ", started ahead of the host" : replayed ? ", replayed from the captured graphs" : "");
     return GGML_STATUS_SUCCESS;
 }
@@ -1879,7 +1889,7 @@ int tp_ahead_replay(hip_backend_ctx * c) {
 // arm decode-ahead for the token after this one (see ahead_launch) -- and, with the chain on, start that step right away.  have_graph: this step was replayed from a captured
 // launch list (one graph, or the tensor-parallel device's graph per stream) that the next step can be started with.
 void ahead_arm(hip_backend_ctx * c, ggml_cgraph * g, const fuse_plan & plan, const std::vector<hip_backend_ctx::scalar_set> & cur_sets, bool have_graph, bool tp) {
-    static const bool ahead_off = getenv("CLLM_HIP_AHEAD") && atoi(getenv("CLLM_HIP_AHEAD")) == 0;
+    const bool ahead_off = !g_opt.ahead;
     auto & A = c->ahead;
     A.armed = false;
     const int nn = ggml_graph_n_nodes(g);
@@ -1898,14 +1908,12 @@ void ahead_arm(hip_backend_ctx * c, ggml_cgraph * g, const fuse_plan & plan, con
     ok = ok && ids && ids->data && n_out <= 8;
     bool has_ids = false;
     for (const auto & ss : cur_sets) { if (ids && ss.ptr == ids->data) has_ids = true; else if ((int64_t) ss.val + 1 >= min_ml || ss.val < 0) ok = false; }
-    static const bool dbg = getenv("CLLM_HIP_AHEAD_DEBUG") != nullptr;
-    if (dbg) HIPB_LOG("ahead: ok=%d has_ids=%d ids=%p n_out=%d out_flag=%d min_ml=%lld sets=%zu out=%s(%s) bytes=%zu", (int) ok, (int) has_ids, ids ? ids->data : nullptr, n_out, (int)((out->flags & GGML_TENSOR_FLAG_OUTPUT) != 0), (long long) min_ml, cur_sets.size(), out->name, ggml_op_name(out->op), ggml_nbytes(out));
+    if (g_opt.ahead_debug) HIPB_LOG("ahead: ok=%d has_ids=%d ids=%p n_out=%d out_flag=%d min_ml=%lld sets=%zu out=%s(%s) bytes=%zu", (int) ok, (int) has_ids, ids ? ids->data : nullptr, n_out, (int)((out->flags & GGML_TENSOR_FLAG_OUTPUT) != 0), (long long) min_ml, cur_sets.size(), out->name, ggml_op_name(out->op), ggml_nbytes(out));
     if (!ok || !has_ids) return;
     A.ids_ptr = ids->data; A.logits_ptr = out->data; A.logits_bytes = ggml_nbytes(out); A.last_sets = cur_sets;
     A.armed = true; A.tp = tp; g_ahead_ctx[c->device] = c;
     // the next step goes out NOW, behind the one just launched (CLLM_HIP_AHEAD_CHAIN=0: when the host reads the logits, round 5's order)
-    static const bool chain = !getenv("CLLM_HIP_AHEAD_CHAIN") || atoi(getenv("CLLM_HIP_AHEAD_CHAIN")) != 0;
-    if (chain) ahead_launch(c, true);
+    if (g_opt.ahead_chain) ahead_launch(c, true);
 }
 
 ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
@@ -1913,8 +1921,7 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
     cllm_set_device(c->device);
     if (c->kernel_error) return GGML_STATUS_FAILED;            // (an earlier launch's in-kernel wait timed out: be_sync)
     void * st = c->stream;
-    static const bool trace = getenv("CLLM_HIP_TRACE") != nullptr;
-    if (trace) {
+    if (g_opt.trace) {
         HIPB_LOG("graph_compute: %d nodes", ggml_graph_n_nodes(g));
         for (int i = 0; i < ggml_graph_n_nodes(g); i++) {
             const ggml_tensor * n = ggml_graph_node(g, i);
@@ -1955,12 +1962,12 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
         }
         g_tp_kv_epoch++; g_tp.plain++; g_tp.last_tp = false; g_tp.rp.valid = false;
     }
-    if (trace) {
+    if (g_opt.trace) {
         for (const fused_mv & f : plan.mvs) if (f.node >= 0) fprintf(stderr, "  plan: mat-vec node %d pro %d%s%s%s\n", f.node, f.pro, f.resid ? " +resid" : "", f.alias ? " STAGED (dst overlaps an input)" : "", f.group >= 0 ? " grouped" : "");
         for (const fused_attn & A : plan.attns) fprintf(stderr, "  plan: attention level %d%s\n", A.level, A.alias ? " STAGED" : "");
         for (int i = 0; i < ggml_graph_n_nodes(g); i++) if (!plan.skip[i]) { const ggml_tensor * n = ggml_graph_node(g, i); if (n->op == GGML_OP_ADD || n->op == GGML_OP_MUL || n->op == GGML_OP_CPY || n->op == GGML_OP_CONT) fprintf(stderr, "  plan: node %d %s launched on its own (alt %d)\n", i, ggml_op_name(n->op), plan.alt[i]); }
     }
-    if (g_stats) g_ws.plan_us += wall_stats::us(ws.t0, wall_stats::clk::now());
+    if (g_opt.stats) g_ws.plan_us += wall_stats::us(ws.t0, wall_stats::clk::now());
     // fused attention: [cos/sin table 1 KB][q | k | v projections][scores of the long-context form]
     // scratch of the fused forms: [cos/sin table 1 KB][q | k | v projections][SiLU(gate)*up activation][scores of the long-context attention]
     size_t qkv_bytes = 0, act_bytes = 0, score_bytes = 0;
@@ -1996,7 +2003,7 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
         plan.alt[G.mul] = ALT_MOE_GATE_UP; plan.moe[G.mul] = (int)(&G - plan.gus.data());
         // the block's router into the same launch (one launch less per sparse-MoE block): the experts read the ids of a router launch whose normalised activation feeds nothing but
         // that router and these two MUL_MAT_IDs, router and experts share one weight type, and whatever else reads the probabilities / ids runs after this node (or is itself fused away)
-        static const bool fold = !getenv("CLLM_HIP_MOE_FOLD") || atoi(getenv("CLLM_HIP_MOE_FOLD")) != 0;
+        const bool fold = g_opt.moe_fold;
         const ggml_tensor * gm = ggml_graph_node(g, G.gate);
         for (size_t ri = 0; fold && ri < plan.routers.size(); ri++) {
             moe_router & R = plan.routers[ri];
@@ -2207,7 +2214,7 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
     return GGML_STATUS_SUCCESS;
 #undef CALL
     };
-    static const bool no_graph = getenv("CLLM_HIP_GRAPH") && atoi(getenv("CLLM_HIP_GRAPH")) == 0;      // default: replay; CLLM_HIP_GRAPH=0 issues every call
+    const bool no_graph = !g_opt.graph;      // default: replay; CLLM_HIP_GRAPH=0 issues every call
     bool replayed = false;
     if (no_graph || c->graph_broken) {
         const ggml_status rs = walk(plan, nullptr);
@@ -2217,7 +2224,7 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
         sig.clear();
         fuse_plan probe = plan;                    // the walk changes the plan (merge decisions): sign on a copy
         sig_writer sw{ sig };
-        static const bool sig_dbg = getenv("CLLM_HIP_SIG_DEBUG") != nullptr;
+        const bool sig_dbg = g_opt.sig_debug;
         static thread_local std::vector<size_t> marks;
         if (sig_dbg) { marks.clear(); sw.marks = &marks; }
         ggml_status rs = walk(probe, &sw);
@@ -2267,7 +2274,7 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
         c->last_sig.swap(sig);
     }
     ahead_arm(c, g, plan, cur_sets, replayed && c->graph_exec != nullptr, false);
-    if (g_stats) {
+    if (g_opt.stats) {
         int a1 = 0, a2 = 0;
         for (const fused_attn & A : plan.attns) (A.level == 2 ? a2 : a1)++;
         for (const merge_group & G : plan.groups) if (G.state == 1) launches -= G.n - 1;
@@ -2399,11 +2406,12 @@ ggml_backend_reg_t ggml_backend_init(void) {
         // (layer split `-ngl "0:16;1:16"`, src/backend.cpp:677-778: a buffer type, a backend, a stream per device; activations cross through cpy_tensor_async +
         // events) then run through the real scheduler on a one-GPU box.  Each ggml device has its own buffer type, so tensors of device 1 are foreign to device 0
         // exactly as on two GPUs; what the physical sharing changes is only that the "peer" copy stays inside one HBM.
+        g_opt.read();
         const int phys = cllm_device_count();
         int n = phys;
-        if (const char * v = getenv("CLLM_HIP_VIRTUAL_DEVICES")) { const int k = atoi(v); if (k > 0 && phys > 0) n = k > 64 ? 64 : k; }
+        if (g_opt.virtual_devices > 0 && phys > 0) n = g_opt.virtual_devices;      // (at most 64: the table clamps)
         // CLLM_HIP_TP=N: ONE logical device over N tensor-parallel ranks (rank r on GPU r % physical: more ranks than GPUs = virtual ranks sharing a GPU) -- tp_graph_compute
-        if (const char * v = getenv("CLLM_HIP_TP")) { const int k = atoi(v); if (k > 1 && phys > 0) { g_tp.n = k > 16 ? 16 : k; n = 1; } }
+        if (g_opt.tp > 1 && phys > 0) { g_tp.n = g_opt.tp; n = 1; }      // (at most 16: the table clamps)
         g_dev_objs.reserve(n);
         for (int i = 0; i < n; i++) {
             auto * d = new hip_device_ctx();

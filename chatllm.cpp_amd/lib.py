@@ -40,6 +40,11 @@ SIGNATURES = {
     "cllm_set_device": (C.c_int, [C.c_int]),
     "cllm_device_info": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "cllm_last_error": (C.c_char_p, []),
+    "cllm_option_is_set": (C.c_int, [C.c_char_p]),
+    "cllm_option_int": (C.c_int, [C.c_char_p]),
+    "cllm_option_real": (C.c_double, [C.c_char_p]),
+    "cllm_option_str": (C.c_char_p, [C.c_char_p]),
+    "cllm_options_describe": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "cllm_type_size": (C.c_size_t, [C.c_int]),
     "cllm_blck_size": (C.c_int, [C.c_int]),
     "cllm_row_size": (C.c_size_t, [C.c_int, C.c_int64]),

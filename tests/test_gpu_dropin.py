@@ -662,6 +662,24 @@ def test_tensor_parallel_device_runs_everything_else_unsharded_and_bit_identical
         assert ids_a == ids_b and np.array_equal(lg_a.view(np.uint32), lg_b.view(np.uint32)), (mp, ngl, extra)      # ... and nothing changed
 
 
+@_REF_BUILT
+def test_a_misspelt_switch_is_said_out_loud_and_changes_nothing(gpu, tmp_path):
+    """CLLM_HIP_TPP=2 (meant: CLLM_HIP_TP) used to run un-sharded without a word: the host's first query of the library's switch table (csrc/options.def) now names it on
+    stderr with its nearest registered neighbour -- and the run is the run with nothing set, ids and every logit word"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import make_ggmm
+    cfg = gpu.synth.config("tiny", max_len=64)
+    mp = str(tmp_path / "m.bin")
+    make_ggmm.write_model(mp, cfg, 12, seed=92)
+    prompt = [5, 9, 42, 300, 7, 99, 250]
+    ids_a, lg_a, err_a = _host_run(tmp_path, mp, "all", 4, prompt, cfg["vocab"])
+    ids_b, lg_b, err_b = _host_run(tmp_path, mp, "all", 4, prompt, cfg["vocab"], CLLM_HIP_TPP="2")
+    said = [ln for ln in err_b.splitlines() if ln.startswith("[cllm] warning: ")]
+    assert len(said) == 1 and "CLLM_HIP_TPP" in said[0] and said[0].endswith("did you mean CLLM_HIP_TP?"), err_b[-1000:]
+    assert "[cllm] " not in err_a and "-> tensor parallel over" not in err_b
+    assert ids_a == ids_b and np.array_equal(lg_a.view(np.uint32), lg_b.view(np.uint32))
+
+
 @_BIG
 @pytest.mark.parametrize("arch,cname,over,prompt_mod", [("qwen2", "qwen2-72b", dict(max_len=256, n_layer=2), 150000), ("llama3", "llama3-8b", dict(max_len=256, n_layer=2), 128000)])
 def test_tensor_parallel_behind_the_boundary_at_real_block_shapes(gpu, tmp_path, arch, cname, over, prompt_mod):
