@@ -55,6 +55,10 @@ LOG2E = 1.4426950408889634
 LOG2E32 = np.float32(LOG2E)
 MUTATIONS = ("no_l_rescale", "no_o_rescale", "lim_plus", "lim_minus", "drop_last_ragged", "leak_hidden", "merge_w1", "merge_l_unweighted",
              "mask_row_next", "kv_head_next", "k_batch0")
+# the single-token form above the long-context threshold (launch_attn_long_flash; tests/attn_long_model.py): the number of positions is read on the device
+# (fattn_args::n_kv_dev) and whole splits lie past it.  ignore_n_kv_dev: the kernel walks all the rows it was given; empty_split_weight_1: a split that saw no
+# key enters the merge with weight 1 and l = 1 instead of (m = -inf, l = 0)
+LONG_MUTATIONS = ("ignore_n_kv_dev", "empty_split_weight_1")
 
 
 def launch_plan(N, H, Hkv, n_kv, scratch=True, div=FA_DIV):
@@ -196,9 +200,11 @@ def emulate(Qop, Kop, Vop, mask, causal_past, scale, n_kv, plan, mutate=()):
     -> out [B, N, H, D] float32, info: rescales [B, N, H] (moves of m_run from a finite value), big_p [B, N, H] (tiles with max p > 2),
     wmin [B, N, H] (the smallest non-zero merge weight, log2)"""
     mutate = set(mutate)
-    assert mutate <= set(MUTATIONS), mutate
+    assert mutate <= set(MUTATIONS) | set(LONG_MUTATIONS), mutate
     B, H, N, D = Qop.shape
     Hkv, rows = Kop.shape[1], Kop.shape[2]
+    if "ignore_n_kv_dev" in mutate:
+        n_kv = rows
     r = H // Hkv
     _, chunk, splits = plan
     f32 = np.float32
@@ -277,6 +283,8 @@ def emulate(Qop, Kop, Vop, mask, causal_past, scale, n_kv, plan, mutate=()):
             M = ms.max(0)
             Ms = np.where(M == -np.inf, f32(0.0), M)
             w = np.exp2(ms - Ms[None]).astype(f32)
+            if "empty_split_weight_1" in mutate:
+                w, ls = np.where(ms == -np.inf, f32(1.0), w), np.where(ms == -np.inf, f32(1.0), ls)
             wmin[b, :, h] = np.min(np.where(w > 0, np.log2(np.where(w > 0, w, 1.0)), 0.0), axis=0)
             if "merge_w1" in mutate:
                 w = np.ones_like(w)
@@ -341,13 +349,14 @@ def make_mask(mode, N, H, n_kv, n_past, plan, rng):
     raise ValueError(mode)
 
 
-def profile(name, D, N, H, Hkv, n_kv, n_past, kv_t, seed, mask_mode=None, rows=None, scratch=True):
+def profile(name, D, N, H, Hkv, n_kv, n_past, kv_t, seed, mask_mode=None, rows=None, scratch=True, plan=None):
     """-> q float32 [H, N, D]; k, v [Hkv, rows, D] float16 or Q8_0 block bytes [Hkv, rows, D / 32 * 34]; mask (make_mask).  rows >= n_kv: the rows of a cache
     view past n_kv continue the profile.  Scores are steered through ONE shared unit direction u added to otherwise Gaussian q and k (whose Gaussian parts are
-    orthogonal to u): scale q.k = level(key) gate(query, head) + Gaussian noise, in base-2 units"""
+    orthogonal to u): scale q.k = level(key) gate(query, head) + Gaussian noise, in base-2 units.  plan: the (decode, chunk, splits) of a launcher other than
+    launch_fattn (tests/attn_long_model.py)"""
     rows = rows or n_kv
     rng = np.random.default_rng([PROFILES.index(name), D, N, H, Hkv, n_kv, n_past, kv_t, seed])
-    plan = launch_plan(N, H, Hkv, n_kv, scratch)
+    plan = plan or launch_plan(N, H, Hkv, n_kv, scratch)
     mask, lead = make_mask(mask_mode, N, H, n_kv, n_past, plan, rng)
     u = rng.choice([-1.0, 1.0], D) / np.sqrt(D)
     orth = lambda g: g - (g @ u)[..., None] * u

@@ -12,6 +12,7 @@ import pytest
 
 import oracle as O
 from conftest import prefill_mode
+from attn_long_model import boundary_rows
 from synth_helpers import rand_blocks, rms_boundary_rows
 
 pytestmark = pytest.mark.gpu
@@ -463,6 +464,34 @@ def test_soft_max(gpu, n0):
     got = gpu.ops.soft_max(gpu.Tensor.from_numpy(x)).numpy()
     # the CPU's AVX2 body (same polynomial, same group sums) and its n mod 8 tail (glibc's expf, glibc_math.h): bit-identical
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), float(np.max(np.abs(got - want)))
+
+
+@pytest.mark.parametrize("n0", [64, 513, 1000, 1024, 4097, 8192, 8200])
+def test_soft_max_rows_on_a_rounding_boundary(gpu, n0):
+    """rows whose reciprocal total sits next to a float rounding boundary (tests/attn_long_model.soft_max_boundary_rows; test_attn_long_model.py checks the
+    condition): soft_total_order_safe (common.h) cannot prove the order of the double total irrelevant there, and k_soft_max, the masked and the fused variant redo
+    it serially in the reference's order.  The random rows of test_soft_max get there once in ~2^20.  Every word must be the oracle's.  By row length the fused
+    op runs k_soft_max<1> (n0 < 512 or no multiple of 8), k_soft_max_causal_reg<8> (1000, 1024), <16> (8192) and k_soft_max_causal_lds (8200: rows above 8192)"""
+    rows = 3
+    x, _ = boundary_rows(n0, rows, 0)
+    x = np.array(x)
+    want = np.zeros_like(x)
+    O.soft_max(O.tensor(x, O.F32, [n0, rows]), None, O.tensor(want, O.F32, [n0, rows]))
+    T, ops = gpu.Tensor, gpu.ops
+    bits = lambda t: t.numpy().reshape(rows, n0).view(np.uint32)
+    assert np.array_equal(bits(ops.soft_max(T.from_numpy(x))), want.view(np.uint32))
+    assert np.array_equal(bits(ops.soft_max_ext(T.from_numpy(x), T.from_numpy(np.zeros((rows, n0), np.float32)), 1.0, 0.0)), want.view(np.uint32))
+    # one fully visible row per head: qlen 1, n_past = n0 - 1, scale 1
+    assert np.array_equal(bits(ops.scale_mask_soft_max(T.from_numpy(x.reshape(rows, 1, n0)), 1.0, n0 - 1)), want.view(np.uint32))
+    dx = T.from_numpy(x)                             # in place, each of the three
+    ops.soft_max(dx, dst=dx)
+    assert np.array_equal(bits(dx), want.view(np.uint32))
+    dx = T.from_numpy(x)
+    ops.soft_max_ext(dx, T.from_numpy(np.zeros((rows, n0), np.float32)), 1.0, 0.0, dst=dx)
+    assert np.array_equal(bits(dx), want.view(np.uint32))
+    dx = T.from_numpy(x.reshape(rows, 1, n0))
+    ops.scale_mask_soft_max(dx, 1.0, n0 - 1, dst=dx)
+    assert np.array_equal(bits(dx), want.view(np.uint32))
 
 
 def test_soft_max_ext_mask(gpu):
