@@ -101,6 +101,12 @@ __device__ __forceinline__ f32x4 tpf_gather4(const tp_fuse_dev * cx, const char 
     return acc;
 }
 
+// What a launcher may ask for as hipFuncAttributeMaxDynamicSharedMemorySize, and the bound its own LDS refusal compares with: the norm prologues (PRO 1 / 5) keep
+// `part[16]` and `scale_w` in STATIC LDS, and static + dynamic must fit the CU's 160 KB -- asking for all 160 KB of an instantiation that has static LDS is refused
+// (hipErrorInvalidValue), which made every PRO 1 / 5 launch with more than 64 KB of dynamic LDS fail (the sparse-MoE router forms of the 32-weight types at K 16384).
+// Every k_gemv_dec launcher (gemv_decode.hip, gemv_moe.hip, gemv_free32.hip, gemv_tp.hip) uses this one constant.
+#define K_GEMV_DEC_MAX_DYN_LDS (160 * 1024 - 256)
+
 // FMT: CLLM_TYPE_Q4_K (8 lanes per 144-byte super-block, activation quantized to Q8_K) or CLLM_TYPE_Q4_0 / Q4_1 / Q8_0 (one lane per
 // 18 / 20 / 34-byte block, activation quantized to Q8_0 / Q8_1).  nblk = weight blocks per row.
 // MOE (MUL_MAT_ID for one token, ggml_compute_forward_mul_mat_id ggml-cpu.c:1432-1678): blockIdx.y is the slot; the slot's expert comes from

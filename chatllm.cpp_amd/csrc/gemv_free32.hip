@@ -18,7 +18,7 @@ int launch_gemv_decode_free(hipStream_t st, int wtype, const void * W, int64_t K
     if (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0) return CLLM_E_UNSUPPORTED;
     if ((pro != 1 && pro != 2) || (epi != 0 && epi != 1) || (epi == 1 && pro != 1)) return CLLM_E_UNSUPPORTED;
     if (K % 32 || K > (pro == 2 ? 32768 : 16384) || nrows <= 0 || (uint64_t) nrows * (uint64_t) cllm_row_size(wtype, K) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (act_row_bytes(K, 32) + 16 * Q32_CHAIN_BYTES > 160 * 1024) return CLLM_E_UNSUPPORTED;
+    if (act_row_bytes(K, 32) + 16 * Q32_CHAIN_BYTES > K_GEMV_DEC_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     if (epi == 1 && (nrows % 2 || (nrows / 2) % 8 || bias || resid)) return CLLM_E_UNSUPPORTED;
     const int64_t units = epi == 1 ? nrows / 2 : nrows;
     int64_t grid = (units + 15) / 16;
@@ -30,7 +30,7 @@ int launch_gemv_decode_free(hipStream_t st, int wtype, const void * W, int64_t K
     if (pro == 1 && npre == 8) return CLLM_E_UNSUPPORTED;
 #define GOF3(FMT_, PRO_, EPI_, NPRE_) do { \
         static uint64_t attr = 0; \
-        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, PRO_, EPI_, NPRE_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); dev_flag_set(attr); } \
+        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, PRO_, EPI_, NPRE_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL((k_gemv_dec<FMT_, PRO_, EPI_, NPRE_, false, true>), dim3((unsigned) grid), dim3(1024), lds, st, px, pw, (const float *) nullptr, (const char *) W, nblk, kfull, nrem, eps, dst, (float *) nullptr, \
                            bias, resid, (unsigned long long *) nullptr, (const int32_t *) nullptr, 0ull, 0, 0); } while (0)
 #define GOF(FMT_) do { \

@@ -9,12 +9,12 @@ int launch_moe_router(hipStream_t st, int wtype, const void * W, int64_t K, int6
                       float * xnorm, float * probs, int32_t * ids, int k) {
     const int kind = wtype == CLLM_TYPE_Q4_K ? 256 : 32;
     if (!is_quant_type(wtype) || K % kind || K % 4 || K > 16384 || n < 1 || n > 64 || k < 1 || k > n) return CLLM_E_UNSUPPORTED;
-    if (act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES > 160 * 1024) return CLLM_E_UNSUPPORTED;
+    if (act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES > K_GEMV_DEC_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     const int kfull = (int)(n / 16), nrem = (int)(n % 16), nblk = (int)(K / kind);
     const size_t lds = act_row_bytes(K, kind) + 16 * (size_t)(wtype == CLLM_TYPE_Q4_K ? Q4K_CHAIN_BYTES : Q32_CHAIN_BYTES) + 2 * 64 * sizeof(float);     // + logits, probabilities
 #define GOR(FMT_, NPRE_) do { \
         static uint64_t attr = 0; \
-        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 1, 2, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); dev_flag_set(attr); } \
+        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 1, 2, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL((k_gemv_dec<FMT_, 1, 2, NPRE_>), dim3(1), dim3(1024), lds, st, px, pw, (const float *) nullptr, (const char *) W, nblk, kfull, nrem, eps, probs, xnorm, \
                            (const float *) nullptr, (const float *) nullptr, (unsigned long long *) nullptr, (const int32_t *) ids, 0ull, 0, k); } while (0)
 #define GORT(FMT_) do { if (K <= 4096) GOR(FMT_, 1); else GOR(FMT_, 4); } while (0)
@@ -33,7 +33,7 @@ int launch_gemv_decode_id_combine(hipStream_t st, int wtype, const void * W, siz
     const int kind = wtype == CLLM_TYPE_Q4_K ? 256 : 32;
     if (!is_quant_type(wtype) || K % kind || K > 32768 || nrows <= 0 || (uint64_t) nrows * (uint64_t) cllm_row_size(wtype, K) >= (1ull << 32) || px_slot_stride > INT32_MAX || px_slot_stride % 4) return CLLM_E_UNSUPPORTED;
     const size_t lds = 2 * act_row_bytes(K, kind) + 16 * (size_t)(wtype == CLLM_TYPE_Q4_K ? Q4K_CHAIN_BYTES : Q32_CHAIN_BYTES);
-    if (2 * act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES > 160 * 1024) return CLLM_E_UNSUPPORTED;
+    if (2 * act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES > K_GEMV_DEC_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     int64_t grid = (nrows + 15) / 16;
     if (grid > device_cu_count()) grid = device_cu_count();
     const int64_t nwaves = grid * 16;
@@ -41,7 +41,7 @@ int launch_gemv_decode_id_combine(hipStream_t st, int wtype, const void * W, siz
     const int npre = K <= 4096 ? 1 : K <= 16384 ? 4 : 8;
 #define GOC(FMT_, NPRE_) do { \
         static uint64_t attr = 0; \
-        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 2, 3, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); dev_flag_set(attr); } \
+        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 2, 3, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL((k_gemv_dec<FMT_, 2, 3, NPRE_>), dim3((unsigned) grid), dim3(1024), lds, st, px, probs, (const float *) nullptr, (const char *) W, nblk, kfull, nrem, 0.0f, dst, (float *) nullptr, \
                            (const float *) nullptr, resid, (unsigned long long *) nullptr, ids, (unsigned long long) w_expert_bytes, (int) px_slot_stride, 0); } while (0)
 #define GOCT(FMT_) do { if (npre == 1) GOC(FMT_, 1); else if (npre == 4) GOC(FMT_, 4); else GOC(FMT_, 8); } while (0)
@@ -62,7 +62,7 @@ int launch_gemv_decode_id_router_silu(hipStream_t st, int wtype, const void * W,
     if (!is_quant_type(wtype) || K % kind || K % 4 || K > 16384 || ne < 1 || ne > 64 || k < 1 || k > ne || nrows <= 0 || nrows % 2 || (nrows / 2) % 8 ||
         (uint64_t) nrows * (uint64_t) cllm_row_size(wtype, K) >= (1ull << 32) || dst_slot_stride > INT32_MAX) return CLLM_E_UNSUPPORTED;
     const size_t lds = act_row_bytes(K, kind) + 16 * (size_t)(wtype == CLLM_TYPE_Q4_K ? Q4K_CHAIN_BYTES : Q32_CHAIN_BYTES) + 3 * 64 * sizeof(float);     // + logits, probabilities, ids
-    if (act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES + 3 * 64 * sizeof(float) > 160 * 1024) return CLLM_E_UNSUPPORTED;
+    if (act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES + 3 * 64 * sizeof(float) > K_GEMV_DEC_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     const int64_t units = nrows / 2;
     int64_t grid = (units + 15) / 16;
     int64_t cap = device_cu_count() / k; if (cap < 1) cap = 1;
@@ -71,7 +71,7 @@ int launch_gemv_decode_id_router_silu(hipStream_t st, int wtype, const void * W,
     const int kfull = (int)(units / nwaves), nrem = (int)(units % nwaves), nblk = (int)(K / kind);
 #define GOX(FMT_, NPRE_) do { \
         static uint64_t attr = 0; \
-        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 1, 5, NPRE_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); dev_flag_set(attr); } \
+        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 1, 5, NPRE_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL((k_gemv_dec<FMT_, 1, 5, NPRE_, true>), dim3((unsigned) grid, (unsigned) k), dim3(1024), lds, st, px, pw, (const float *) Wr, (const char *) W, nblk, kfull, nrem, eps, dst, probs, \
                            (const float *) nullptr, (const float *) nullptr, (unsigned long long *) nullptr, (const int32_t *) ids, (unsigned long long) w_expert_bytes, ne, (int) dst_slot_stride); } while (0)
 #define GOXT(FMT_) do { if (K <= 4096) GOX(FMT_, 1); else GOX(FMT_, 4); } while (0)

@@ -21,7 +21,7 @@ int launch_gemv_decode_tp_scatter(hipStream_t st, int wtype, const void * W, int
     const int kind = wtype == CLLM_TYPE_Q4_K ? 256 : 32;
     if (!is_quant_type(wtype) || !ctx_dev || (pro != 2 && pro != 3)) return CLLM_E_UNSUPPORTED;
     if (K % kind || K > (pro == 2 ? 32768 : 16384) || nrows <= 0 || (uint64_t) nrows * (uint64_t) cllm_row_size(wtype, K) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES > 160 * 1024) return CLLM_E_UNSUPPORTED;
+    if (act_row_bytes(K, kind) + 16 * Q32_CHAIN_BYTES > K_GEMV_DEC_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     int64_t grid = (nrows + 15) / 16;
     if (grid > device_cu_count()) grid = device_cu_count();
     const int64_t nwaves = grid * 16;
@@ -30,7 +30,7 @@ int launch_gemv_decode_tp_scatter(hipStream_t st, int wtype, const void * W, int
     const int npre = K <= 4096 ? 1 : K <= 16384 ? 4 : 8;
 #define GOS(FMT_, PRO_, NPRE_) do { \
         static uint64_t attr = 0; \
-        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, PRO_, 4, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); dev_flag_set(attr); } \
+        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, PRO_, 4, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL((k_gemv_dec<FMT_, PRO_, 4, NPRE_>), dim3((unsigned) grid), dim3(1024), lds, st, px, (const float *) nullptr, (const float *) nullptr, (const char *) W, nblk, kfull, nrem, 0.0f, \
                            (float *) nullptr, (float *) nullptr, (const float *) nullptr, (const float *) nullptr, (unsigned long long *) nullptr, (const int32_t *) ctx_dev, 0ull, 0, site); } while (0)
 #define GOSF(FMT_) do { \
@@ -51,7 +51,7 @@ int launch_gemv_decode_tp_gather(hipStream_t st, int wtype, const void * W, int6
     if (K % kind || K > 16384 || nrows <= 0 || (uint64_t) nrows * (uint64_t) cllm_row_size(wtype, K) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
     if (epi == 1 && (nrows % 2 || (nrows / 2) % 8 || bias)) return CLLM_E_UNSUPPORTED;
     const size_t lds = act_row_bytes(K, kind) + 16 * (size_t)(wtype == CLLM_TYPE_Q4_K ? Q4K_CHAIN_BYTES : Q32_CHAIN_BYTES) + (size_t) K * 4;      // + the row copy of the serial RMS fallback
-    if (lds > 160 * 1024 - 256) return CLLM_E_UNSUPPORTED;
+    if (lds > K_GEMV_DEC_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     const int64_t units = epi == 1 ? nrows / 2 : nrows;
     int64_t grid = (units + 15) / 16;
     if (grid > device_cu_count()) grid = device_cu_count();
@@ -60,7 +60,7 @@ int launch_gemv_decode_tp_gather(hipStream_t st, int wtype, const void * W, int6
     const int npre = K <= 4096 ? 1 : 4;
 #define GOG(FMT_, EPI_, NPRE_) do { \
         static uint64_t attr = 0; \
-        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 5, EPI_, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)); dev_flag_set(attr); } \
+        if (lds > 64 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT_, 5, EPI_, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS)); dev_flag_set(attr); } \
         hipLaunchKernelGGL((k_gemv_dec<FMT_, 5, EPI_, NPRE_>), dim3((unsigned) grid), dim3(1024), lds, st, px, pw, (const float *) nullptr, (const char *) W, nblk, kfull, nrem, eps, \
                            dst, xout, bias, (const float *) nullptr, g_tp_ts, (const int32_t *) ctx_dev, 0ull, site, 0); } while (0)
 #define GOGF(FMT_) do { \

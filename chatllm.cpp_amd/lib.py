@@ -9,7 +9,11 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "chatllm_hip.h")
 
 
 class CllmError(RuntimeError):
-    pass
+    """rc: the cllm_status of the failed call (None where no call was made)"""
+
+    def __init__(self, msg, rc=None):
+        super().__init__(msg)
+        self.rc = rc
 
 
 class CTensor(C.Structure):
@@ -209,7 +213,7 @@ def get():
 def check(rc, what=""):
     if rc != 0:
         msg = get().cllm_last_error()
-        raise CllmError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+        raise CllmError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}", rc)
 
 
 def require_gpu():

@@ -66,6 +66,21 @@ class Tensor:
             _l.check(_l.get().cllm_stream_sync(None), "sync")
         return t
 
+    @staticmethod
+    def from_strided(raw, type_, ne, nb):
+        """raw: the bytes of a whole buffer (uint8), described as a tensor of strides nb: padded rows, padded expert matrices.  raw() reads the buffer back"""
+        raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+        ne = [int(x) for x in ne] + [1] * (4 - len(ne))
+        nb = [int(x) for x in nb]
+        while len(nb) < 4:
+            nb.append(nb[-1] * ne[len(nb) - 1])
+        last = sum((ne[i] - 1) * nb[i] for i in range(1, 4)) + row_size(type_, ne[0])
+        assert last <= raw.nbytes, f"the strides reach byte {last} of a buffer of {raw.nbytes}"
+        t = Tensor(type_, ne, nb, Buffer(raw.nbytes))
+        _l.check(_l.get().cllm_memcpy_h2d(t.data_ptr(), raw.ctypes.data_as(C.c_void_p), raw.nbytes, None), "h2d")
+        _l.check(_l.get().cllm_stream_sync(None), "sync")
+        return t
+
     def nbytes(self):
         return self.nb[3] * self.ne[3]
 

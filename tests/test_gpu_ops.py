@@ -638,6 +638,8 @@ def test_moe_router_ops_bit_exact(gpu, n0, n1, n2, k):
 
 @pytest.mark.parametrize("t,K,F,E,k", [(O.Q4_K, 4096, 1024, 8, 2), (O.Q8_0, 512, 264, 4, 2), (O.Q4_0, 1024, 512, 8, 3), (O.Q4_1, 256, 64, 8, 2)])
 def test_mul_mat_id_silu_mul_equals_the_four_nodes(gpu, t, K, F, E, k):
+    """cllm_op_mul_mat_id_silu_mul against the four device nodes, bit for bit (both sides run k_gemv_dec<.., MOE>).
+    The oracle anchor of this form, at every launch geometry: tests/test_gpu_moe.py."""
     ops, T = gpu.ops, gpu.Tensor
     wg = T.from_numpy(rand_blocks(t, F * E, K, rng), t, [K, F, E])
     wu = T.from_numpy(rand_blocks(t, F * E, K, rng), t, [K, F, E])
@@ -716,7 +718,8 @@ def test_moe_router_equals_the_node_sequence(gpu, t, K, ne, k):
                                        (O.Q4_K, 8192, 128, 33, 4), (O.Q4_K, 4096, 14336, 8, 2)])
 def test_moe_router_gate_up_equals_the_two_launches(gpu, t, K, F, E, k):
     """cllm_op_moe_router_gate_up (the router redone inside the experts' gate / up launch: one launch less per sparse-MoE block) = cllm_op_moe_router followed by
-    cllm_op_mul_mat_id_silu_mul on its outputs: probabilities, ids and SiLU(gate) * up of every slot, bit for bit"""
+    cllm_op_mul_mat_id_silu_mul on its outputs: probabilities, ids and SiLU(gate) * up of every slot, bit for bit.
+    The oracle anchor of this form, at every launch geometry: tests/test_gpu_moe.py."""
     ops, T = gpu.ops, gpu.Tensor
     wr = T.from_numpy(rand_blocks(t, E, K, rng, d_scale=0.05), t, [K, E])
     wg = T.from_numpy(rand_blocks(t, F * E, K, rng), t, [K, F, E])
@@ -733,7 +736,8 @@ def test_moe_router_gate_up_equals_the_two_launches(gpu, t, K, F, E, k):
 @pytest.mark.parametrize("t,K,H,E,with_resid", [(O.Q4_K, 14336, 4096, 8, True), (O.Q4_K, 512, 256, 8, False), (O.Q8_0, 512, 264, 4, True), (O.Q4_0, 1024, 100, 8, True),
                                                 (O.Q4_1, 4096, 512, 3, False), (O.Q4_K, 20480, 64, 4, True)])
 def test_mul_mat_id_combine_equals_the_two_launches(gpu, t, K, H, E, with_resid):
-    """cllm_op_mul_mat_id_combine = cllm_op_mul_mat_id (down experts, two slots) -> cllm_op_moe_combine, bit for bit; also in place on the residual"""
+    """cllm_op_mul_mat_id_combine = cllm_op_mul_mat_id (down experts, two slots) -> cllm_op_moe_combine, bit for bit; also in place on the residual.
+    The oracle anchor of this form, at every launch geometry: tests/test_gpu_moe.py."""
     ops, T = gpu.ops, gpu.Tensor
     w = T.from_numpy(rand_blocks(t, H * E, K, rng), t, [K, H, E])
     x = T.from_numpy(rng.standard_normal((1, 2, K)).astype(np.float32))
@@ -754,6 +758,8 @@ def test_mul_mat_id_combine_equals_the_two_launches(gpu, t, K, H, E, with_resid)
 
 @pytest.mark.parametrize("H,k,T,ne,with_resid", [(4096, 2, 1, 8, True), (256, 2, 5, 8, False), (100, 4, 3, 16, True)])
 def test_moe_combine_equals_the_node_sequence(gpu, H, k, T, ne, with_resid):
+    """cllm_op_moe_combine against the device nodes GET_ROWS -> SUM_ROWS -> DIV -> MUL -> ADD of the slot views (-> ADD of the residual), bit for bit.
+    The same chain on the CPU oracle: tests/test_gpu_moe.py."""
     ops, T_ = gpu.ops, gpu.Tensor
     e = T_.from_numpy(rng.standard_normal((T, k, H)).astype(np.float32))
     pr = rng.standard_normal((T, ne)).astype(np.float32)

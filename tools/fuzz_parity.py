@@ -83,7 +83,9 @@ def main():
     def mul_mat_id():
         t = int(rng.choice(QT))
         K = O.BLCK[t] * int(rng.integers(1, 5)) if O.BLCK[t] == 256 else 32 * int(rng.choice([2, 3, 8, 16, 33]))
-        N, E, U, Tk = int(rng.choice([8, 40, 100])), int(rng.choice([4, 8])), int(rng.choice([1, 2, 3])), int(rng.choice([1, 1, 2, 5]))
+        N, E, U, Tk = int(rng.choice([8, 40, 100, 1064])), int(rng.choice([4, 8])), int(rng.choice([1, 2, 3])), int(rng.choice([1, 1, 2, 5]))
+        if N == 1064:               # one token, up to 8 slots: the slot cap CUs / U leaves the one-token kernel full rounds of rows and a remainder (the row loop, not only its tail)
+            U, Tk = int(rng.choice([1, 2, 3, 8])), 1
         w = rand_blocks(t, N * E, K, rng)
         nb1 = int(rng.choice([1, U]))
         x = rng.standard_normal((Tk, nb1, K)).astype(np.float32)
