@@ -445,6 +445,10 @@ enum { SCRATCH_ATTN_SCORES = 0, SCRATCH_X16 = 1 };
 void * stream_scratch(hipStream_t st, int kind, size_t need);
 void stream_scratch_release(hipStream_t st);
 int launch_mmvq_act(hipStream_t st, int wtype, const void * W, int64_t K, int64_t nrows, const void * act, float * dst, const float * bias, const float * resid);
+// the decode mat-vecs' prologues (k_gemv_dec, k_gemv_rows, k_gemv_rows32, k_gemv_team32): NPRE, the activation groups of four values a thread holds, and the longest row by
+// prologue -- the plain-quantize forms (pro 2, 4) make two passes (NPRE 8); the norm and interleaved-pair forms have no such instantiation
+static inline int gemv_npre(int64_t K) { return K <= 4096 ? 1 : K <= 16384 ? 4 : 8; }
+static inline int64_t gemv_k_max(int pro) { return (pro == 2 || pro == 4) ? 32768 : 16384; }
 int launch_gemv_decode(hipStream_t st, int wtype, const void * W, int64_t K, int64_t nrows, int pro, const float * px, const float * pw, float eps, int epi, float * dst, const float * bias, const float * resid, const float * padd = nullptr, float * xout = nullptr);
 bool prefill_f16_enabled();
 // how MUL_MAT with more than 32 activation columns and the prompt's attention block are computed (capi.hip; CLLM_PREFILL=exact | fast | f16, cllm_set_prefill_mode):

@@ -104,7 +104,7 @@ __device__ __forceinline__ f32x4 tpf_gather4(const tp_fuse_dev * cx, const char 
 // What a launcher may ask for as hipFuncAttributeMaxDynamicSharedMemorySize, and the bound its own LDS refusal compares with: the norm prologues (PRO 1 / 5) keep
 // `part[16]` and `scale_w` in STATIC LDS, and static + dynamic must fit the CU's 160 KB -- asking for all 160 KB of an instantiation that has static LDS is refused
 // (hipErrorInvalidValue), which made every PRO 1 / 5 launch with more than 64 KB of dynamic LDS fail (the sparse-MoE router forms of the 32-weight types at K 16384).
-// Every k_gemv_dec launcher (gemv_decode.hip, gemv_moe.hip, gemv_free32.hip, gemv_tp.hip) uses this one constant.
+// Used in one place, gemv_decode_launch.h: gemv_dec_make_plan refuses against it, gemv_dec_launch asks for it -- for every k_gemv_dec launcher.
 #define K_GEMV_DEC_MAX_DYN_LDS (160 * 1024 - 256)
 
 // FMT: CLLM_TYPE_Q4_K (8 lanes per 144-byte super-block, activation quantized to Q8_K) or CLLM_TYPE_Q4_0 / Q4_1 / Q8_0 (one lane per

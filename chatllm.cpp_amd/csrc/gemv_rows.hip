@@ -242,7 +242,7 @@ static int gemv_rows_go(hipStream_t st, const void * W, int64_t K, int64_t nrows
     // projections are a draw or slower: one unit per wave leaves no steady state); 2: everything it can take; 8 / 4: that too, with RPW forced
     static const int mode = opt_int(OPT_CLLM_GEMV_ROWS);
     if (!mode || K % 256 || pro < 1 || pro > 4 || nrows <= 0 || (uint64_t) nrows * (uint64_t)(K / 256 * 144) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (K > ((pro == 2 || pro == 4) ? 32768 : 16384)) return CLLM_E_UNSUPPORTED;
+    if (K > gemv_k_max(pro)) return CLLM_E_UNSUPPORTED;
     if (epi == 1 && (pro != 1 || bias || resid)) return CLLM_E_UNSUPPORTED;
     if (epi == 2 && (pro != 1 || !bias || !resid)) return CLLM_E_UNSUPPORTED;
     const int nblk = (int)(K / 256), cus = device_cu_count();
@@ -256,7 +256,7 @@ static int gemv_rows_go(hipStream_t st, const void * W, int64_t K, int64_t nrows
     if (epi == 2 && grid > 256) return CLLM_E_UNSUPPORTED;          // (the partial arrays hold 256 entries)
     const size_t lds = act_row_bytes(K, 256) + 16 * (size_t) ROWS_NS * ROWS_SLOT_BYTES;
     if (lds > 159 * 1024) return CLLM_E_UNSUPPORTED;      // (+ the prologue's static 128 bytes)
-    const int npre = K <= 4096 ? 1 : K <= 16384 ? 4 : 8;
+    const int npre = gemv_npre(K);
 #define GOR(PRO_, EPI_, NPRE_, RPW_) do { \
         static uint64_t attr = 0; \
         if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_rows<PRO_, EPI_, NPRE_, RPW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024)); dev_flag_set(attr); } \

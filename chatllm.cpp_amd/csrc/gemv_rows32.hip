@@ -227,7 +227,7 @@ int launch_gemv_rows32(hipStream_t st, int wtype, const void * W, int64_t K, int
     if (!mode || (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0)) return CLLM_E_UNSUPPORTED;
     const int bs = wtype == CLLM_TYPE_Q8_0 ? 34 : wtype == CLLM_TYPE_Q4_1 ? 20 : 18;
     if (K % 32 || ((K / 32) * bs) % 4 || pro < 1 || pro > 4 || nrows <= 0 || ((uintptr_t) W & 3) || (uint64_t) nrows * (uint64_t)(K / 32 * bs) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (K > ((pro == 2 || pro == 4) ? 32768 : 16384)) return CLLM_E_UNSUPPORTED;
+    if (K > gemv_k_max(pro)) return CLLM_E_UNSUPPORTED;
     if (epi == 1 && (pro != 1 || bias || resid || nrows % 2)) return CLLM_E_UNSUPPORTED;
     const int nblk = (int)(K / 32), cus = device_cu_count();
     // rows per wave: 8 where that leaves >= 8 units per CU (gate/up, lm_head: 17.5 vs 29 us, 63 vs 120 us on Llama-3-8B Q4_0); the hidden-sized outputs have too few
@@ -241,7 +241,7 @@ int launch_gemv_rows32(hipStream_t st, int wtype, const void * W, int64_t K, int
     const int grid = (nunits + 15) / 16 < cus ? (nunits + 15) / 16 : cus;
     const size_t lds = act_row_bytes(K, wtype == CLLM_TYPE_Q4_1 ? ACT_Q8_1 : ACT_Q8_0) + ((wtype == CLLM_TYPE_Q4_0 && R32_C0_PLANE) ? (size_t) K : 0) + 16 * (size_t) R32_REC_BYTES;
     if (lds > 159 * 1024) return CLLM_E_UNSUPPORTED;
-    const int npre = K <= 4096 ? 1 : K <= 16384 ? 4 : 8;
+    const int npre = gemv_npre(K);
 #define GOR(FMT_, PRO_, EPI_, NPRE_, RPW_) do { \
         static uint64_t attr = 0; \
         if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_rows32<FMT_, PRO_, EPI_, NPRE_, RPW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024)); dev_flag_set(attr); } \

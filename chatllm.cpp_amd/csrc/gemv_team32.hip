@@ -388,7 +388,7 @@ int launch_gemv_team32(hipStream_t st, int wtype, const void * W, int64_t K, int
     if (!mode || epi != 0 || (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0)) return CLLM_E_UNSUPPORTED;
     const int bs = wtype == CLLM_TYPE_Q8_0 ? 34 : wtype == CLLM_TYPE_Q4_1 ? 20 : 18;
     if (K % 32 || ((K / 32) * bs) % 4 || pro < 1 || pro > 4 || nrows <= 0 || nrows % 8 || ((uintptr_t) W & 3) || (uint64_t) nrows * (uint64_t)(K / 32 * bs) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (K > ((pro == 2 || pro == 4) ? 32768 : 16384) || K < 256) return CLLM_E_UNSUPPORTED;
+    if (K > gemv_k_max(pro) || K < 256) return CLLM_E_UNSUPPORTED;
     const int nblk = (int)(K / 32), cus = device_cu_count();
     const int nunits = (int)(nrows / 8);
     // teams per workgroup = units per CU (each team takes ONE unit at a time; more than 4 units per CU: the other kernels have enough rows)
@@ -407,7 +407,7 @@ int launch_gemv_team32(hipStream_t st, int wtype, const void * W, int64_t K, int
     if (lds > 158 * 1024) return CLLM_E_UNSUPPORTED;
     unsigned * g_t32_err = nullptr;
     { const int erc = kernel_error_word(&g_t32_err); if (erc) return erc; }
-    const int npre = K <= 4096 ? 1 : K <= 16384 ? 4 : 8;
+    const int npre = gemv_npre(K);
 #define GOT(FMT_, PRO_, NPRE_) do { \
         static uint64_t attr = 0; \
         if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_team32<FMT_, PRO_, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024)); dev_flag_set(attr); } \

@@ -938,6 +938,167 @@ def test_mul_mat_vec_fused_equals_the_node_sequence(gpu, t, K, N, pro):
     assert np.array_equal(out.numpy(), want)
 
 
+# ---- launch_gemv_decode's (PRO, EPI, NPRE) leaves that no other test launches THROUGH k_gemv_dec (the 32-weight formats' default launchers, gemv_rows32.hip / gemv_team32.hip, are
+#      switched off; Q4_K's gemv_rows.hip takes only 32+ units of 8 rows per CU).  One K per NPRE, the smallest that selects it: one weight block (NPRE 1), 4352 (NPRE 4), 16640
+#      (NPRE 8: the plain-quantize prologues only).  Rows: 40 (no full round: kfull 0, nrem only), 16 * CUs + 24 (one full round + a remainder); EPI 1: 8 gate / up pairs.
+#      PRO 3 (interleaved gate / up pairs in front of down_proj) has no operator of its own: cllm_bench_gemv_fused launches it, once before and once inside its timed region.
+_DEC_LEAVES = [(O.Q4_K, 1, 1, 4, 0), (O.Q4_K, 3, 0, 1, 0), (O.Q4_K, 3, 0, 4, 0),
+               (O.Q4_0, 1, 1, 4, 0), (O.Q4_0, 1, 0, 4, 0), (O.Q4_0, 4, 0, 4, 0), (O.Q4_0, 4, 0, 8, 0), (O.Q4_0, 3, 0, 1, 0), (O.Q4_0, 3, 0, 4, 0),
+               (O.Q4_1, 1, 1, 4, 0), (O.Q4_1, 4, 0, 8, 0), (O.Q4_1, 3, 0, 1, 0), (O.Q4_1, 3, 0, 4, 0),
+               (O.Q8_0, 1, 1, 4, 0), (O.Q8_0, 4, 0, 8, 0), (O.Q8_0, 3, 0, 1, 0), (O.Q8_0, 3, 0, 4, 0),
+               # launch_gemv_decode_free's (free 1: the free-order tier on for the nodes AND the fused launch -- one order, per row, whatever the prologue)
+               (O.Q4_0, 1, 1, 4, 1), (O.Q4_0, 2, 0, 8, 1), (O.Q4_1, 1, 1, 4, 1), (O.Q4_1, 2, 0, 8, 1), (O.Q8_0, 1, 1, 4, 1), (O.Q8_0, 2, 0, 8, 1)]
+_DEC_LEAF_CASES = [leaf + (rows,) for leaf in _DEC_LEAVES for rows in (("pairs",) if leaf[2] == 1 else ("rem", "round"))]
+
+
+@pytest.mark.parametrize("t,pro,epi,npre,free,rows", _DEC_LEAF_CASES)
+def test_k_gemv_dec_leaf_equals_the_node_sequence(gpu, rows32_mode, team32_mode, t, pro, epi, npre, free, rows):
+    ops, T, L = gpu.ops, gpu.Tensor, gpu.lib.get()
+    n_cu = C.c_int(0)
+    gpu.lib.check(L.cllm_device_info(0, None, 0, None, None, C.byref(n_cu)), "device_info")
+    K = {1: 256 if t == O.Q4_K else 32, 4: 4352, 8: 16640}[npre]
+    N = {"rem": 40, "round": 16 * n_cu.value + 24, "pairs": 16}[rows]
+    assert (epi == 1) == (rows == "pairs")
+    w = T.from_numpy(rand_blocks(t, N, K, rng), t, [K, N])
+    L.cllm_set_decode_free_order(free)
+    try:
+        x = T.from_numpy(rng.standard_normal((1, K)).astype(np.float32))
+        g = T.from_numpy((1 + 0.1 * rng.standard_normal((1, K))).astype(np.float32))
+        r = T.from_numpy(rng.standard_normal((1, N)).astype(np.float32))
+        if pro == 1:
+            act = ops.rms_norm_mul(x, T.from_numpy(g.numpy().reshape(K)), 1e-5)
+        elif pro == 2:
+            act = x
+        else:
+            act = ops.silu_mul(x, g)
+        y = ops.mul_mat(w, act)                                                             # the nodes, on the launchers every other test leaves them on
+        if epi == 1:
+            y = y.numpy().reshape(N // 2, 2)
+            gate, up = (T.from_numpy(np.ascontiguousarray(y[:, i]).reshape(1, N // 2)) for i in range(2))
+            want = ops.mul(ops.silu(gate), up).numpy().reshape(-1)
+        else:
+            want = ops.add(y, r).numpy().reshape(-1)
+        n_out = N // 2 if epi == 1 else N
+        out = T(gpu.F32, [n_out, 1])
+        cw = w.c()
+        rows32_mode(0); team32_mode(0)
+        if pro == 3:
+            xgu = T.from_numpy(np.ascontiguousarray(np.stack([x.numpy().reshape(K), g.numpy().reshape(K)], axis=1)).reshape(1, 2 * K))      # (gate_e, up_e) pairs
+            ptrs, us = (C.c_void_p * 1)(w.data_ptr().value), C.c_float()
+            gpu.lib.check(L.cllm_bench_gemv_fused(None, t, ptrs, 1, K, N, 3, xgu.data_ptr(), None, 1e-5, 0, out.data_ptr(), r.data_ptr(), 1, C.byref(us)), "bench_gemv_fused")
+        else:
+            gpu.lib.check(L.cllm_op_mul_mat_vec_fused(None, C.byref(cw), pro, x.data_ptr(), g.data_ptr() if pro != 2 else None, 1e-5, epi,
+                                                       None if epi == 1 else r.data_ptr(), out.data_ptr()), "fused")
+    finally:
+        L.cllm_set_decode_free_order(0)
+    assert np.array_equal(out.numpy().reshape(-1).view(np.uint32), want.view(np.uint32))
+
+
+# ---- the tensor-parallel leaves (gemv_tp.hip) on two virtual ranks of one stream (cllm_tp_fused_create_group): the same K per NPRE and the same row counts as above
+_TYPES4 = [O.Q4_K, O.Q4_0, O.Q4_1, O.Q8_0]
+_DEC_K = {1: lambda t: 256 if t == O.Q4_K else 32, 4: lambda t: 4352, 8: lambda t: 16640}
+
+
+def _dec_rows(gpu, rows):
+    n_cu = C.c_int(0)
+    gpu.lib.check(gpu.lib.get().cllm_device_info(0, None, 0, None, None, C.byref(n_cu)), "device_info")
+    return {"rem": 40, "round": 16 * n_cu.value + 24, "pairs": 16}[rows]
+
+
+def _tp_group(gpu, nranks, max_n):
+    objs = (C.c_void_p * nranks)()
+    gpu.lib.check(gpu.lib.get().cllm_tp_fused_create_group(nranks, (C.c_int * nranks)(*([0] * nranks)), 3, max_n, objs), "create_group")
+    return objs
+
+
+@pytest.mark.parametrize("t", _TYPES4)
+@pytest.mark.parametrize("pro,npre", [(2, 1), (2, 4), (2, 8), (3, 1), (3, 4)])
+@pytest.mark.parametrize("rows", ["rem", "round"])
+def test_k_gemv_dec_tp_scatter_leaf_sends_the_rows_of_the_plain_mat_vec(gpu, rows32_mode, team32_mode, t, pro, npre, rows):
+    """EPI 4: every rank's granules are the bits of its plain mat-vec (pro 3: of the mat-vec over silu(gate) * up); gathered: resid + (p0 + p1), on both ranks"""
+    T, L = gpu.Tensor, gpu.lib.get()
+    K, N, site = _DEC_K[npre](t), _dec_rows(gpu, rows), 1
+    w = T.from_numpy(rand_blocks(t, N, K, rng), t, [K, N])                              # (both ranks: the same weights over different activations)
+    cw = w.c()
+    resid = T.from_numpy(rng.standard_normal((1, N)).astype(np.float32))
+    objs = _tp_group(gpu, 2, N)
+    try:
+        rows32_mode(0); team32_mode(0)                                                  # the plain mat-vec too: k_gemv_dec's order is every launcher's, this keeps it one kernel
+        xs, parts = [], []
+        for r in range(2):
+            gate, up = (rng.standard_normal((1, K)).astype(np.float32) for _ in range(2))
+            y = T(gpu.F32, [N, 1])
+            if pro == 2:
+                xs.append(T.from_numpy(gate))
+                gpu.lib.check(L.cllm_op_mul_mat_vec_fused(None, C.byref(cw), 2, xs[r].data_ptr(), None, 0.0, 0, None, y.data_ptr()), "plain")
+            else:
+                xs.append(T.from_numpy(np.ascontiguousarray(np.stack([gate.reshape(K), up.reshape(K)], axis=1)).reshape(1, 2 * K)))      # (gate_e, up_e) pairs
+                tg, tu = T.from_numpy(gate), T.from_numpy(up)
+                gpu.lib.check(L.cllm_op_mul_mat_vec_fused(None, C.byref(cw), 4, tg.data_ptr(), tu.data_ptr(), 0.0, 0, None, y.data_ptr()), "plain")
+            parts.append(y.numpy().reshape(N).copy())
+        for r in range(2):
+            gpu.lib.check(L.cllm_tp_fused_advance(objs[r], None), "advance")
+        for r in range(2):
+            gpu.lib.check(L.cllm_op_mul_mat_vec_tp_scatter(None, C.byref(cw), pro, xs[r].data_ptr(), objs[r], site), "scatter")
+        want = resid.numpy().reshape(N) + (parts[0] + parts[1])
+        for r in range(2):
+            out = T(gpu.F32, [N, 1])
+            gpu.lib.check(L.cllm_op_tp_gather_residual(None, resid.data_ptr(), N, objs[r], site, out.data_ptr()), "gather_residual")
+            gpu.lib.check(L.cllm_stream_sync(None), "sync")
+            assert np.array_equal(out.numpy().reshape(N).view(np.uint32), want.view(np.uint32)), r
+            assert L.cllm_tp_fused_error(objs[r]) == 0
+    finally:
+        for r in range(2):
+            L.cllm_tp_fused_destroy(objs[r])
+
+
+@pytest.mark.parametrize("t", _TYPES4)
+@pytest.mark.parametrize("npre", [1, 4])
+@pytest.mark.parametrize("epi,rows", [(0, "rem"), (0, "round"), (1, "pairs")])
+def test_k_gemv_dec_tp_gather_leaf_equals_the_node_sequence(gpu, rows32_mode, team32_mode, t, npre, epi, rows):
+    """PRO 5: dst = W . quantize(RMS_NORM(px + all-reduced partials of the site) * pw) (+ bias | SiLU(gate) * up), xout = px + the partials -- against
+    cllm_op_tp_gather_residual -> RMS_NORM -> MUL -> MUL_MAT (-> ADD | -> SILU -> MUL), to the bit, dst and xout"""
+    ops, T, L = gpu.ops, gpu.Tensor, gpu.lib.get()
+    K, N, site = _DEC_K[npre](t), _dec_rows(gpu, rows), 2
+    k0 = _DEC_K[1](t)                                                                   # the partials of the site: two ranks' K rows over one weight block each
+    w0 = T.from_numpy(rand_blocks(t, K, k0, rng), t, [k0, K])
+    cw0 = w0.c()
+    w = T.from_numpy(rand_blocks(t, N, K, rng), t, [K, N])
+    cw = w.c()
+    px = T.from_numpy(rng.standard_normal((1, K)).astype(np.float32))
+    pw = T.from_numpy((1 + 0.1 * rng.standard_normal(K)).astype(np.float32))
+    bias = T.from_numpy(rng.standard_normal((1, N)).astype(np.float32))
+    objs = _tp_group(gpu, 2, K)
+    try:
+        x0 = [T.from_numpy(rng.standard_normal((1, k0)).astype(np.float32)) for _ in range(2)]
+        for r in range(2):
+            gpu.lib.check(L.cllm_tp_fused_advance(objs[r], None), "advance")
+        for r in range(2):
+            gpu.lib.check(L.cllm_op_mul_mat_vec_tp_scatter(None, C.byref(cw0), 2, x0[r].data_ptr(), objs[r], site), "scatter")
+        for r in range(2):
+            xref = T(gpu.F32, [K, 1])
+            gpu.lib.check(L.cllm_op_tp_gather_residual(None, px.data_ptr(), K, objs[r], site, xref.data_ptr()), "gather_residual")
+            y = ops.mul_mat(w, ops.rms_norm_mul(T.from_numpy(xref.numpy().reshape(1, K)), pw, 1e-5))
+            if epi == 1:
+                y = y.numpy().reshape(N // 2, 2)
+                gate, up = (T.from_numpy(np.ascontiguousarray(y[:, i]).reshape(1, N // 2)) for i in range(2))
+                want = ops.mul(ops.silu(gate), up).numpy().reshape(-1)
+            else:
+                want = ops.add(y, bias).numpy().reshape(-1)
+            out, xout = T(gpu.F32, [N // 2 if epi == 1 else N, 1]), T(gpu.F32, [K, 1])
+            rows32_mode(0); team32_mode(0)
+            gpu.lib.check(L.cllm_op_mul_mat_vec_tp_gather(None, C.byref(cw), px.data_ptr(), pw.data_ptr(), 1e-5, epi, None if epi == 1 else bias.data_ptr(), out.data_ptr(),
+                                                          objs[r], site, xout.data_ptr()), "gather")
+            rows32_mode(1); team32_mode(1)
+            gpu.lib.check(L.cllm_stream_sync(None), "sync")
+            assert np.array_equal(out.numpy().reshape(-1).view(np.uint32), want.view(np.uint32)), r
+            assert np.array_equal(xout.numpy().reshape(-1).view(np.uint32), xref.numpy().reshape(-1).view(np.uint32)), r
+            assert L.cllm_tp_fused_error(objs[r]) == 0
+    finally:
+        for r in range(2):
+            L.cllm_tp_fused_destroy(objs[r])
+
+
 @pytest.mark.parametrize("K", [1280, 14336, 17408])
 def test_fused_plain_quantize_prologue_on_ties_and_zero_blocks(gpu, K):
     """the 16-values-per-lane quantize_row_q8_K of the decode mat-vec's plain-quantize prologue (quant16_q8_K): super-blocks whose largest magnitude occurs with BOTH

@@ -94,6 +94,27 @@ def test_rccl_all_reduce_inside_the_decode_graph_matches_the_host_callback(gpu, 
     a.close(); b.close(); c.close()
 
 
+@pytest.mark.parametrize("wtype", ["Q4_K", "Q4_0", "Q4_1", "Q8_0"])
+def test_unfused_all_reduce_folded_into_the_next_norm_mat_vec_equals_the_node_path(gpu, wtype):
+    """launch_gemv_decode's padd / xout form (PRO 1, K <= 4096, NPRE 1; EPI 0 for qkv, EPI 1 for gate / up): with an all-reduce that is NOT fused into the mat-vecs, the
+    decode step hands the all-reduced o / down partial to the next RMS_NORM mat-vec, which adds it to the residual stream (xout = px + padd, the other ping-pong buffer) in
+    its prologue.  The form has no operator of its own; the decoder is its only caller.  Free-running greedy steps against the node-by-node path (ADD nodes): every logit
+    word equal -- a lost padd, or an xout that is not px + padd, changes the residual stream of every later layer."""
+    cfg = gpu.synth.config("small", max_len=64, ffn=2048)
+    w = _rank0_shard_model(gpu, cfg, getattr(gpu, wtype), seed=5)
+    prompt = np.random.default_rng(4).integers(0, cfg["vocab"], 5).astype(np.int32)
+    a, b = (gpu.Llama(cfg, w, tp_rank=0, tp_size=2) for _ in range(2))
+    for m in (a, b):
+        m.set_allreduce(lambda stream, buf, n: None)          # the identity all-reduce of a one-rank "group"
+    la, lb = a.forward(prompt), b.forward(prompt)
+    for step in range(4):
+        assert np.array_equal(la.view(np.uint32), lb.view(np.uint32)), step
+        t = int(np.argmax(la))
+        la, lb = a.decode_fused_logits(t), b.forward([t])
+    assert np.array_equal(la.view(np.uint32), lb.view(np.uint32))
+    a.close(); b.close()
+
+
 def test_bench_tp_setup_under_torchrun_with_one_rank(gpu):
     """bench.py's multi-GPU set-up (torch first, id broadcast, collective success flag, communicator bound to the runner) walked with
     ONE rank under the driver's launcher -- the only part of the N > 1 path a single-GPU box can execute"""
