@@ -17,17 +17,14 @@
 //     [row][bytes] in a ring of NS slots per wave; the consumer waits with s_waitcnt vmcnt(3 x slots issued later) -- loads retire in
 //     order, so counting only our own DMA instructions is safe whatever else the compiler has in flight (it can only make the wait stricter).
 // Units of RPW rows are dealt CU-interleaved (unit u -> workgroup u % grid, wave (u / grid) % 16), so every CU gets the same share.
-#include "common.h"
-#include "quant_dev.h"
+#include "gemv_act.h"
 #include "q4k.h"
+#include "gemv_rows_launch.h"
 
 #define ROWS_SLOT_BYTES 2304
 #ifndef ROWS_NS
 #define ROWS_NS 3
 #endif
-
-__device__ __forceinline__ float silu_poly_r(float x) { return x / (1.0f + ggml_expf_poly(0.0f - x)); }
-__device__ __forceinline__ float silu_any_r(float x, bool body) { return body ? silu_poly_r(x) : x / (1.0f + libm_expf(-x)); }
 
 // one DMA instruction: 64 (or fewer: EXEC) lanes x 16 bytes, global (base + voff) -> LDS (lds_dst + 16 * lane)
 __device__ __forceinline__ void dma16(const char * base /* wave-uniform */, unsigned voff, unsigned lds_dst /* wave-uniform */) {
@@ -52,17 +49,10 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
     const int K = nblk * 256;
     const unsigned nb01 = (unsigned) nblk * 144u;
 
-    // ---- (1) this thread's activation groups: loads issued before anything else (as k_gemv_dec) ----
-    const float * gp = (PRO == 1 || PRO == 4) ? pw : PRO == 3 ? px + 4 : px;
-    constexpr int vmul = PRO == 3 ? 2 : 1;
+    // ---- (1) this thread's activation groups: loads issued before anything else (gemv_act.h) ----
     const int e0 = tid * 4;
     f32x4 vv[NPRE], gg[NPRE];
-#pragma unroll
-    for (int u = 0; u < NPRE; u++) {
-        const int e = e0 + u * 4096, ec = e < K ? e : 0;
-        vv[u] = *(const f32x4 *)(px + ec * vmul);
-        if (PRO != 2) gg[u] = *(const f32x4 *)(gp + ec * vmul);
-    }
+    gemv_act_load<PRO, NPRE>(vv, gg, px, pw, K, e0);
 
     // ---- (2) this wave's stream of slots: units (k * 16 + wave) * grid + block, SPU slots each; the first NS slots fly during the prologue ----
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -95,32 +85,9 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
 #pragma unroll
     for (int p = 0; p < NS; p++) issue();
 
-    // ---- (3) the activation row: [RMS_NORM * weight | SiLU * up |] quantize -> LDS (act layout of common.h), exactly as k_gemv_dec ----
-    float scale = 1.0f;
-    if (PRO == 1) {
-        __shared__ double part[16];
-        const double sum = NPRE == 1 ? rms_block_sumsq_1024_one(vv[0], e0 < K, part) : rms_block_sumsq_1024(px, K, vv[0], part);
-        scale = rms_scale(sum, K, eps, px, nullptr, part);
-    }
-    const int nv = K & ~7;
-#pragma unroll
-    for (int u = 0; u < NPRE; u++) {
-        const int e = e0 + u * 4096;
-        if (e < K) {
-            f32x4 v = vv[u];
-            if (PRO == 3) {
-                const f32x4 p0 = vv[u], p1 = gg[u];
-                v.x = silu_any_r(p0.x, e + 0 < nv) * p0.y; v.y = silu_any_r(p0.z, e + 1 < nv) * p0.w;
-                v.z = silu_any_r(p1.x, e + 2 < nv) * p1.y; v.w = silu_any_r(p1.z, e + 3 < nv) * p1.w;
-            }
-            if (PRO == 4) {
-                const f32x4 g = gg[u];
-                v.x = silu_any_r(v.x, e + 0 < nv) * g.x; v.y = silu_any_r(v.y, e + 1 < nv) * g.y; v.z = silu_any_r(v.z, e + 2 < nv) * g.z; v.w = silu_any_r(v.w, e + 3 < nv) * g.w;
-            }
-            if (PRO == 1) { const f32x4 g = gg[u]; v.x = (v.x * scale) * g.x; v.y = (v.y * scale) * g.y; v.z = (v.z * scale) * g.z; v.w = (v.w * scale) * g.w; }
-            quant4_store<256, false>(lds, K, e, lane, v);
-        }
-    }
+    // ---- (3) the activation row: [RMS_NORM * weight | SiLU * up |] quantize -> LDS (gemv_act.h) ----
+    __shared__ double part[16];
+    gemv_act_store<256, false, false, PRO, NPRE>(lds, vv, gg, px, K, eps, e0, lane, part);
     __syncthreads();
     if (EPI != 2 && nmine == 0) return;                               // (EPI 2: every wave meets the barriers of the arg-max tail)
 
@@ -187,8 +154,7 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
         issue();                                                      // refill the slot just consumed
         cq++;
         if (++cs == SPU) {                                            // RPW rows complete
-            float hsum = acc;
-            hsum = hsum + dpp_f<DPP_QUAD_XOR1>(hsum); hsum = hsum + dpp_f<DPP_QUAD_XOR2>(hsum); hsum = hsum + dpp_f<DPP_HALF_MIRROR>(hsum);
+            const float hsum = gemv_hsum8(acc);
             float ms = accm;                                          // lanes j & 3 = [m0 m2 m1 m3]
             ms = ms + dpp_f<DPP_QUAD_XOR1>(ms); ms = ms + dpp_f<DPP_QUAD_XOR2>(ms);
             float v = hsum + ms;
@@ -196,20 +162,11 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
             if (EPI == 1) {                                           // rows alternate gate_u, up_u
                 const float up = RPW == 8 ? dpp_f<DPP_ROW_ROR8>(v) : __shfl_down(v, 16, 64);
                 const bool st = RPW == 8 ? (lane & 15) == 0 : (lane & 31) == 0;
-                if (st) dst[unit * (RPW / 2) + (RPW == 8 ? lane >> 4 : lane >> 5)] = silu_poly_r(v) * up;
+                if (st) dst[unit * (RPW / 2) + (RPW == 8 ? lane >> 4 : lane >> 5)] = silu_poly(v) * up;
             } else {
                 const int row = unit * RPW + rowg;
                 const bool st = RPW == 8 ? j == 0 : (lane & 15) == 0;
-                if (EPI != 2 && (bias || resid)) {                    // the unit's RPW values through the scalar cache: their own counter, no wait on the DMA stream
-                    float bsel = 0.0f, rsel = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < RPW; q++) {
-                        if (bias)  { const float x = uniform_load_f32(bias  + (size_t) unit * RPW + q); bsel = rowg == q ? x : bsel; }
-                        if (resid) { const float x = uniform_load_f32(resid + (size_t) unit * RPW + q); rsel = rowg == q ? x : rsel; }
-                    }
-                    if (bias)  v = v + bsel;
-                    if (resid) v = v + rsel;
-                }
+                if (EPI != 2 && (bias || resid)) v = gemv_bias_resid<RPW>(v, bias, resid, (size_t) unit * RPW, rowg);
                 if (st) dst[row] = v;
                 if (EPI == 2 && st && (v > bestv || (v == bestv && row < besti))) { bestv = v; besti = row; }
             }
@@ -241,9 +198,7 @@ static int gemv_rows_go(hipStream_t st, const void * W, int64_t K, int64_t nrows
     // 0: off; 1 (default): only where it measured faster than k_gemv_dec -- many rows per CU (lm_head: 78 -> 62 us; gate/up and the small
     // projections are a draw or slower: one unit per wave leaves no steady state); 2: everything it can take; 8 / 4: that too, with RPW forced
     static const int mode = opt_int(OPT_CLLM_GEMV_ROWS);
-    if (!mode || K % 256 || pro < 1 || pro > 4 || nrows <= 0 || (uint64_t) nrows * (uint64_t)(K / 256 * 144) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (K > gemv_k_max(pro)) return CLLM_E_UNSUPPORTED;
-    if (epi == 1 && (pro != 1 || bias || resid)) return CLLM_E_UNSUPPORTED;
+    if (!mode || !gemv_row_shape_ok(CLLM_TYPE_Q4_K, K, nrows, pro, epi, bias, resid)) return CLLM_E_UNSUPPORTED;
     if (epi == 2 && (pro != 1 || !bias || !resid)) return CLLM_E_UNSUPPORTED;
     const int nblk = (int)(K / 256), cus = device_cu_count();
     if (mode == 1 && nrows / 8 < 32 * (int64_t) cus) return CLLM_E_UNSUPPORTED;
@@ -254,24 +209,18 @@ static int gemv_rows_go(hipStream_t st, const void * W, int64_t K, int64_t nrows
     const int nunits = (int)(nrows / rpw);
     int grid = nunits < cus ? nunits : cus;
     if (epi == 2 && grid > 256) return CLLM_E_UNSUPPORTED;          // (the partial arrays hold 256 entries)
-    const size_t lds = act_row_bytes(K, 256) + 16 * (size_t) ROWS_NS * ROWS_SLOT_BYTES;
-    if (lds > 159 * 1024) return CLLM_E_UNSUPPORTED;      // (+ the prologue's static 128 bytes)
-    const int npre = gemv_npre(K);
-#define GOR(PRO_, EPI_, NPRE_, RPW_) do { \
-        static uint64_t attr = 0; \
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_rows<PRO_, EPI_, NPRE_, RPW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024)); dev_flag_set(attr); } \
-        hipLaunchKernelGGL((k_gemv_rows<PRO_, EPI_, NPRE_, RPW_>), dim3((unsigned) grid), dim3(1024), lds, st, px, pw, (const char *) W, nblk, nunits, eps, dst, bias, resid); } while (0)
-#define GOP(RPW_) do { \
-        if (pro == 1 && epi == 1) { if (npre == 1) GOR(1, 1, 1, RPW_); else GOR(1, 1, 4, RPW_); } \
-        else if (pro == 1 && epi == 2) { if (npre == 1) GOR(1, 2, 1, RPW_); else GOR(1, 2, 4, RPW_); } \
-        else if (pro == 1)        { if (npre == 1) GOR(1, 0, 1, RPW_); else GOR(1, 0, 4, RPW_); } \
-        else if (pro == 2)        { if (npre == 1) GOR(2, 0, 1, RPW_); else if (npre == 4) GOR(2, 0, 4, RPW_); else GOR(2, 0, 8, RPW_); } \
-        else if (pro == 4)        { if (npre == 1) GOR(4, 0, 1, RPW_); else if (npre == 4) GOR(4, 0, 4, RPW_); else GOR(4, 0, 8, RPW_); } \
-        else                      { if (npre == 1) GOR(3, 0, 1, RPW_); else GOR(3, 0, 4, RPW_); } } while (0)
-    if (rpw == 8) GOP(8); else GOP(4);
-#undef GOP
-#undef GOR
-    LAUNCH_CHECK();
+    const size_t lds = gemv_row_lds(CLLM_TYPE_Q4_K, K, false, 16 * (size_t) ROWS_NS * ROWS_SLOT_BYTES);
+    if (lds > K_GEMV_ROWS_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
+    auto go = [&](auto rpw_c, auto epi_c) {
+        return gemv_row_by_pro_npre(pro, gemv_npre(K), [&](auto pro_c, auto npre_c) {
+            constexpr int PRO = decltype(pro_c)::value, EPI = decltype(epi_c)::value;
+            if constexpr (EPI != 0 && PRO != 1) return (int) CLLM_E_UNSUPPORTED;      // (refused above: these epilogues exist behind the norm prologue only)
+            else return gemv_row_launch<k_gemv_rows<PRO, EPI, decltype(npre_c)::value, decltype(rpw_c)::value>, K_GEMV_ROWS_MAX_DYN_LDS>(st, grid, lds, px, pw, (const char *) W, nblk, nunits, eps, dst, bias, resid);
+        });
+    };
+    auto by_epi = [&](auto rpw_c) { return epi == 1 ? go(rpw_c, gemv_c<1>()) : epi == 2 ? go(rpw_c, gemv_c<2>()) : go(rpw_c, gemv_c<0>()); };
+    const int rc = rpw == 8 ? by_epi(gemv_c<8>()) : by_epi(gemv_c<4>());
+    if (rc) return rc;
     if (grid_out) *grid_out = grid;
     return CLLM_OK;
 }

@@ -10,10 +10,10 @@
 // Q4_0 gate/up).  Here a step is RPW rows x LPR = 64 / RPW blocks: lane (r, t) owns block t of row r in a step (same loads, same integer work), the records are
 // [row][slot of A][t], and EVERY lane runs a chain: lane (r, j) walks the LPR blocks of row r for slot j -- LPR fma per step instead of 64 (RPW 8: 8).
 // RPW is picked by the launcher so that there are at least ~8 units per CU (gate/up, lm_head: 8; the hidden-sized outputs: 2 or 4).
-#include "common.h"
-#include "quant_dev.h"
+#include "gemv_act.h"
 #include "q4k.h"
 #include "q32.h"
+#include "gemv_rows_launch.h"
 
 #ifndef R32_P
 #define R32_P 4
@@ -21,9 +21,6 @@
 
 typedef int r32_i4 __attribute__((ext_vector_type(4)));
 #define R32_REC_BYTES (64 * 9 * 4 + 2 * 256)          // per wave: RPW rows x 9 sub-rows (8 slots + d_w d_x) x LPR floats, then Q4_1's m_w[64], s_a[64]
-
-__device__ __forceinline__ float r32_silu(float x) { return x / (1.0f + ggml_expf_poly(0.0f - x)); }
-__device__ __forceinline__ float r32_silu_any(float x, bool body) { return body ? r32_silu(x) : x / (1.0f + libm_expf(-x)); }
 
 template <int FMT, int PRO, int EPI, int NPRE, int RPW>
 __global__ void __launch_bounds__(1024) k_gemv_rows32(const float * __restrict__ px, const float * __restrict__ pw, const char * __restrict__ W, int nblk, int nunits, float eps,
@@ -40,17 +37,10 @@ __global__ void __launch_bounds__(1024) k_gemv_rows32(const float * __restrict__
     constexpr bool IS_40 = !IS_Q8 && !IS_41, NEED_C0 = IS_40 && R32_C0_PLANE;
     const unsigned arb = (unsigned) act_row_bytes(K, IS_41 ? ACT_Q8_1 : ACT_Q8_0);      // the activation row; Q4_0: then K bytes of c0[block][AVX lane] (int32)
 
-    // ---- (1) this thread's activation groups: loads issued before anything else (as k_gemv_dec) ----
-    const float * gp = (PRO == 1 || PRO == 4) ? pw : PRO == 3 ? px + 4 : px;
-    constexpr int vmul = PRO == 3 ? 2 : 1;
+    // ---- (1) this thread's activation groups: loads issued before anything else (gemv_act.h) ----
     const int e0 = tid * 4;
     f32x4 vv[NPRE], gg[NPRE];
-#pragma unroll
-    for (int u = 0; u < NPRE; u++) {
-        const int e = e0 + u * 4096, ec = e < K ? e : 0;
-        vv[u] = *(const f32x4 *)(px + ec * vmul);
-        if (PRO != 2) gg[u] = *(const f32x4 *)(gp + ec * vmul);
-    }
+    gemv_act_load<PRO, NPRE>(vv, gg, px, pw, K, e0);
 
     // ---- (2) this wave's units (RPW consecutive rows): (k * 16 + wave) * grid + block; the first P steps fly during the prologue.
     //          A block's bytes are loaded as the 4-byte aligned window around it (q32.h); rows are whole dwords, so a block starts in the upper half of its
@@ -84,33 +74,9 @@ __global__ void __launch_bounds__(1024) k_gemv_rows32(const float * __restrict__
 #pragma unroll
     for (int p = 0; p < P; p++) issue(p);
 
-    // ---- (3) the activation row: [RMS_NORM * weight | SiLU * up |] quantize -> LDS (act layout of common.h), exactly as k_gemv_dec ----
-    float scale = 1.0f;
-    if (PRO == 1) {
-        __shared__ double part[16];
-        const double sum = NPRE == 1 ? rms_block_sumsq_1024_one(vv[0], e0 < K, part) : rms_block_sumsq_1024(px, K, vv[0], part);
-        scale = rms_scale(sum, K, eps, px, nullptr, part);
-    }
-    const int nv = K & ~7;
-#pragma unroll
-    for (int u = 0; u < NPRE; u++) {
-        const int e = e0 + u * 4096;
-        if (e < K) {
-            f32x4 v = vv[u];
-            if (PRO == 3) {
-                const f32x4 p0 = vv[u], p1 = gg[u];
-                v.x = r32_silu_any(p0.x, e + 0 < nv) * p0.y; v.y = r32_silu_any(p0.z, e + 1 < nv) * p0.w;
-                v.z = r32_silu_any(p1.x, e + 2 < nv) * p1.y; v.w = r32_silu_any(p1.z, e + 3 < nv) * p1.w;
-            }
-            if (PRO == 4) {
-                const f32x4 g = gg[u];
-                v.x = r32_silu_any(v.x, e + 0 < nv) * g.x; v.y = r32_silu_any(v.y, e + 1 < nv) * g.y; v.z = r32_silu_any(v.z, e + 2 < nv) * g.z; v.w = r32_silu_any(v.w, e + 3 < nv) * g.w;
-            }
-            if (PRO == 1) { const f32x4 g = gg[u]; v.x = (v.x * scale) * g.x; v.y = (v.y * scale) * g.y; v.z = (v.z * scale) * g.z; v.w = (v.w * scale) * g.w; }
-            quant4_store<32, IS_41>(lds, K, e, lane, v);
-            if (NEED_C0) *(int *)(lds + arb + e) = dot4(0xf8f8f8f8u, *(const uint32_t *)(lds + e), 0);      // Q4_0: (nib - 8) . a = nib . a + c0, c0 = (-8, -8, -8, -8) . a per (block, AVX lane)
-        }
-    }
+    // ---- (3) the activation row: [RMS_NORM * weight | SiLU * up |] quantize -> LDS, Q4_0's c0 plane behind it (gemv_act.h) ----
+    __shared__ double part[16];
+    gemv_act_store<32, IS_41, NEED_C0, PRO, NPRE>(lds, vv, gg, px, K, eps, e0, lane, part);
     __syncthreads();
     if (nmine == 0) return;
 
@@ -188,25 +154,15 @@ __global__ void __launch_bounds__(1024) k_gemv_rows32(const float * __restrict__
 #endif
             wave_lds_fence();
             if (++cs == S) {                                          // RPW rows complete: hsum_float_8 over the 8 slots (neighbour exchanges), epilogue, store
-                float hsum = acc;
-                hsum = hsum + dpp_f<DPP_QUAD_XOR1>(hsum); hsum = hsum + dpp_f<DPP_QUAD_XOR2>(hsum); hsum = hsum + dpp_f<DPP_HALF_MIRROR>(hsum);
+                const float hsum = gemv_hsum8(acc);
                 float v = IS_41 ? hsum + accs : hsum;
                 if (cu < nmine) {
                     const int unit = u0 + cu * ustride;
                     if (EPI == 1) {                                   // rows alternate gate_u, up_u: the up row is the next lane group
                         const float up = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + LPR) & 63) * 4, __float_as_int(v)));
-                        if (t == 0 && !(r & 1)) dst[unit * (RPW / 2) + (r >> 1)] = r32_silu(v) * up;
+                        if (t == 0 && !(r & 1)) dst[unit * (RPW / 2) + (r >> 1)] = silu_poly(v) * up;
                     } else {
-                        if (bias || resid) {                          // the unit's RPW values through the scalar cache (no wait on the weight prefetch)
-                            float bsel = 0.0f, rsel = 0.0f;
-#pragma unroll
-                            for (int q = 0; q < RPW; q++) {
-                                if (bias)  { const float x = uniform_load_f32(bias  + (size_t) unit * RPW + q); bsel = r == q ? x : bsel; }
-                                if (resid) { const float x = uniform_load_f32(resid + (size_t) unit * RPW + q); rsel = r == q ? x : rsel; }
-                            }
-                            if (bias)  v = v + bsel;
-                            if (resid) v = v + rsel;
-                        }
+                        if (bias || resid) v = gemv_bias_resid<RPW>(v, bias, resid, (size_t) unit * RPW, r);
                         if (t == 0) dst[(size_t) unit * RPW + r] = v;
                     }
                 }
@@ -224,11 +180,8 @@ int launch_gemv_rows32(hipStream_t st, int wtype, const void * W, int64_t K, int
                        const float * bias, const float * resid) {
     if (g_rows32_mode < 0) g_rows32_mode = opt_int(OPT_CLLM_GEMV_ROWS32);      // 0: off, 2 / 4 / 8: that many rows per wave where the shape allows
     const int mode = g_rows32_mode;
-    if (!mode || (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0)) return CLLM_E_UNSUPPORTED;
-    const int bs = wtype == CLLM_TYPE_Q8_0 ? 34 : wtype == CLLM_TYPE_Q4_1 ? 20 : 18;
-    if (K % 32 || ((K / 32) * bs) % 4 || pro < 1 || pro > 4 || nrows <= 0 || ((uintptr_t) W & 3) || (uint64_t) nrows * (uint64_t)(K / 32 * bs) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (K > gemv_k_max(pro)) return CLLM_E_UNSUPPORTED;
-    if (epi == 1 && (pro != 1 || bias || resid || nrows % 2)) return CLLM_E_UNSUPPORTED;
+    if (!mode || wtype == CLLM_TYPE_Q4_K || ((uintptr_t) W & 3) || !gemv_row_shape_ok(wtype, K, nrows, pro, epi, bias, resid)) return CLLM_E_UNSUPPORTED;
+    if (epi == 1 && nrows % 2) return CLLM_E_UNSUPPORTED;
     const int nblk = (int)(K / 32), cus = device_cu_count();
     // rows per wave: 8 where that leaves >= 8 units per CU (gate/up, lm_head: 17.5 vs 29 us, 63 vs 120 us on Llama-3-8B Q4_0); the hidden-sized outputs have too few
     // rows for that -- one row per wave (k_gemv_dec) keeps 16 waves per CU busy and measured faster than 2 or 4 rows side by side (o: 7.3 vs 10.4 us, down: 21 vs 33 us).
@@ -239,26 +192,18 @@ int launch_gemv_rows32(hipStream_t st, int wtype, const void * W, int64_t K, int
     if (!rpw) return CLLM_E_UNSUPPORTED;
     const int nunits = (int)(nrows / rpw);
     const int grid = (nunits + 15) / 16 < cus ? (nunits + 15) / 16 : cus;
-    const size_t lds = act_row_bytes(K, wtype == CLLM_TYPE_Q4_1 ? ACT_Q8_1 : ACT_Q8_0) + ((wtype == CLLM_TYPE_Q4_0 && R32_C0_PLANE) ? (size_t) K : 0) + 16 * (size_t) R32_REC_BYTES;
-    if (lds > 159 * 1024) return CLLM_E_UNSUPPORTED;
-    const int npre = gemv_npre(K);
-#define GOR(FMT_, PRO_, EPI_, NPRE_, RPW_) do { \
-        static uint64_t attr = 0; \
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_rows32<FMT_, PRO_, EPI_, NPRE_, RPW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024)); dev_flag_set(attr); } \
-        hipLaunchKernelGGL((k_gemv_rows32<FMT_, PRO_, EPI_, NPRE_, RPW_>), dim3((unsigned) grid), dim3(1024), lds, st, px, pw, (const char *) W, nblk, nunits, eps, dst, bias, resid); } while (0)
-#define GOW(FMT_, PRO_, EPI_, NPRE_) do { if (rpw == 2) GOR(FMT_, PRO_, EPI_, NPRE_, 2); else GOR(FMT_, PRO_, EPI_, NPRE_, 4); } while (0)
-#define GOW1(FMT_, EPI_, NPRE_) do { if (rpw == 8) GOR(FMT_, 1, EPI_, NPRE_, 8); else GOW(FMT_, 1, EPI_, NPRE_); } while (0)
-#define GOP(FMT_) do { \
-        if (pro == 1 && epi == 1) { if (npre == 1) GOW1(FMT_, 1, 1); else GOW1(FMT_, 1, 4); } \
-        else if (pro == 1)        { if (npre == 1) GOW1(FMT_, 0, 1); else GOW1(FMT_, 0, 4); } \
-        else if (pro == 2)        { if (npre == 1) GOW(FMT_, 2, 0, 1); else if (npre == 4) GOW(FMT_, 2, 0, 4); else GOW(FMT_, 2, 0, 8); } \
-        else if (pro == 4)        { if (npre == 1) GOW(FMT_, 4, 0, 1); else if (npre == 4) GOW(FMT_, 4, 0, 4); else GOW(FMT_, 4, 0, 8); } \
-        else                      { if (npre == 1) GOW(FMT_, 3, 0, 1); else GOW(FMT_, 3, 0, 4); } } while (0)
-    if (wtype == CLLM_TYPE_Q4_0) GOP(CLLM_TYPE_Q4_0); else if (wtype == CLLM_TYPE_Q4_1) GOP(CLLM_TYPE_Q4_1); else GOP(CLLM_TYPE_Q8_0);
-#undef GOP
-#undef GOW1
-#undef GOW
-#undef GOR
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    const size_t lds = gemv_row_lds(wtype, K, wtype == CLLM_TYPE_Q4_0 && R32_C0_PLANE, 16 * (size_t) R32_REC_BYTES);
+    if (lds > K_GEMV_ROWS32_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
+    auto go = [&](auto fmt, auto epi_c) {
+        return gemv_row_by_pro_npre(pro, gemv_npre(K), [&](auto pro_c, auto npre_c) {
+            constexpr int FMT = decltype(fmt)::value, PRO = decltype(pro_c)::value, EPI = decltype(epi_c)::value, NPRE = decltype(npre_c)::value;
+            auto run = [&](auto rpw_c) {
+                return gemv_row_launch<k_gemv_rows32<FMT, PRO, EPI, NPRE, decltype(rpw_c)::value>, K_GEMV_ROWS32_MAX_DYN_LDS>(st, grid, lds, px, pw, (const char *) W, nblk, nunits, eps, dst, bias, resid);
+            };
+            if constexpr (PRO == 1) return rpw == 8 ? run(gemv_c<8>()) : rpw == 2 ? run(gemv_c<2>()) : run(gemv_c<4>());
+            else if constexpr (EPI == 0) return rpw == 2 ? run(gemv_c<2>()) : run(gemv_c<4>());
+            else return (int) CLLM_E_UNSUPPORTED;                      // (refused above: EPI 1 and 8 rows per wave exist behind the norm prologue only)
+        });
+    };
+    return gemv_row_by_type32(wtype, [&](auto fmt) { return pro == 1 && epi == 1 ? go(fmt, gemv_c<1>()) : go(fmt, gemv_c<0>()); });
 }

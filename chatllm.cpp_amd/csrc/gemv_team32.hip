@@ -12,10 +12,10 @@
 //     the chain wave waits for the count, walks the round's records with the LDS reads two steps ahead of the fmas, and publishes the number of rounds it has
 //     consumed, which frees the slots of that parity.  All inside the workgroup, bounded waits (a timeout raises an error word instead of hanging).
 // Teams per workgroup = units per CU (1, 2, 3 or 4: 16, 8, 5 or 4 waves per team); the teams' chain waves sit on different SIMDs.
-#include "common.h"
-#include "quant_dev.h"
+#include "gemv_act.h"
 #include "q4k.h"
 #include "q32.h"
+#include "gemv_rows_launch.h"
 
 // weight steps in flight per emit wave (requested before the prologue, which lasts about as long as the whole matrix takes to stream)
 // weight steps in flight per emit wave
@@ -27,8 +27,6 @@ typedef int t32_i4 __attribute__((ext_vector_type(4)));
 #define T32_SLOT_BYTES (64 * 9 * 4 + 2 * 256)          // one step's records: [row r][slot j or d][t] floats (8 x 9 x 8), then Q4_1's m_w[64], s_a[64]
 #define T32_SPINS (1 << 20)
 
-__device__ __forceinline__ float t32_silu(float x) { return x / (1.0f + ggml_expf_poly(0.0f - x)); }
-__device__ __forceinline__ float r32_silu_any(float x, bool body) { return body ? t32_silu(x) : x / (1.0f + libm_expf(-x)); }
 __device__ __forceinline__ unsigned t32_lds_load(const unsigned * p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void t32_lds_store(unsigned * p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
@@ -50,7 +48,7 @@ __global__ void __launch_bounds__(1024) k_gemv_team32(const float * __restrict__
     const unsigned nb01 = (unsigned) nblk * (unsigned) BS;
     const unsigned arb = (unsigned) act_row_bytes(K, IS_41 ? ACT_Q8_1 : ACT_Q8_0);      // the activation row; Q4_0: then K bytes of c0[block][AVX lane] (int32)
 
-    // ---- (1) this thread's activation groups: loads issued before anything else (as k_gemv_dec) ----
+    // ---- (1) this thread's activation groups: loads issued before anything else (the text of gemv_act.h's gemv_act_load(), kept in place here) ----
     const float * gp = (PRO == 1 || PRO == 4) ? pw : PRO == 3 ? px + 4 : px;
     constexpr int vmul = PRO == 3 ? 2 : 1;
     const int e0 = tid * 4;
@@ -111,7 +109,7 @@ __global__ void __launch_bounds__(1024) k_gemv_team32(const float * __restrict__
         for (int p = 0; p < P; p++) issue(p);
     }
 
-    // ---- (3) the activation row: [RMS_NORM * weight | SiLU * up |] quantize -> LDS (act layout of common.h), exactly as k_gemv_dec ----
+    // ---- (3) the activation row: [RMS_NORM * weight | SiLU * up |] quantize -> LDS (act layout of common.h), the text of gemv_act.h's gemv_act_store(), kept in place here (profiles/gemv_row_kernels_shared.txt section 5) ----
     float scale = 1.0f;
     if (PRO == 1) {
         __shared__ double part[16];
@@ -126,12 +124,12 @@ __global__ void __launch_bounds__(1024) k_gemv_team32(const float * __restrict__
             f32x4 v = vv[u];
             if (PRO == 3) {
                 const f32x4 p0 = vv[u], p1 = gg[u];
-                v.x = r32_silu_any(p0.x, e + 0 < nv) * p0.y; v.y = r32_silu_any(p0.z, e + 1 < nv) * p0.w;
-                v.z = r32_silu_any(p1.x, e + 2 < nv) * p1.y; v.w = r32_silu_any(p1.z, e + 3 < nv) * p1.w;
+                v.x = silu_any(p0.x, e + 0 < nv) * p0.y; v.y = silu_any(p0.z, e + 1 < nv) * p0.w;
+                v.z = silu_any(p1.x, e + 2 < nv) * p1.y; v.w = silu_any(p1.z, e + 3 < nv) * p1.w;
             }
             if (PRO == 4) {
                 const f32x4 g = gg[u];
-                v.x = r32_silu_any(v.x, e + 0 < nv) * g.x; v.y = r32_silu_any(v.y, e + 1 < nv) * g.y; v.z = r32_silu_any(v.z, e + 2 < nv) * g.z; v.w = r32_silu_any(v.w, e + 3 < nv) * g.w;
+                v.x = silu_any(v.x, e + 0 < nv) * g.x; v.y = silu_any(v.y, e + 1 < nv) * g.y; v.z = silu_any(v.z, e + 2 < nv) * g.z; v.w = silu_any(v.w, e + 3 < nv) * g.w;
             }
             if (PRO == 1) { const f32x4 g = gg[u]; v.x = (v.x * scale) * g.x; v.y = (v.y * scale) * g.y; v.z = (v.z * scale) * g.z; v.w = (v.w * scale) * g.w; }
             quant4_store<32, IS_41>(lds, K, e, lane, v);
@@ -292,8 +290,7 @@ __global__ void __launch_bounds__(1024) k_gemv_team32(const float * __restrict__
             accs = __builtin_fmaf(cur.m1.x, cur.s1.x, accs); accs = __builtin_fmaf(cur.m1.y, cur.s1.y, accs); accs = __builtin_fmaf(cur.m1.z, cur.s1.z, accs); accs = __builtin_fmaf(cur.m1.w, cur.s1.w, accs);
         }
         if (++s_in_unit == S) {                                        // 8 rows complete: hsum_float_8 over the 8 slots, epilogue, store
-            float hsum = acc;
-            hsum = hsum + dpp_f<DPP_QUAD_XOR1>(hsum); hsum = hsum + dpp_f<DPP_QUAD_XOR2>(hsum); hsum = hsum + dpp_f<DPP_HALF_MIRROR>(hsum);
+            const float hsum = gemv_hsum8(acc);
             float v = IS_41 ? hsum + accs : hsum;
             const int unit = u0 + ku * ustride;
             if (bias)  v = v + bv;
@@ -385,10 +382,8 @@ int launch_gemv_team32(hipStream_t st, int wtype, const void * W, int64_t K, int
                        const float * bias, const float * resid) {
     if (g_team32_mode < 0) g_team32_mode = opt_int(OPT_CLLM_GEMV_TEAM32);
     const int mode = g_team32_mode;
-    if (!mode || epi != 0 || (wtype != CLLM_TYPE_Q4_0 && wtype != CLLM_TYPE_Q4_1 && wtype != CLLM_TYPE_Q8_0)) return CLLM_E_UNSUPPORTED;
-    const int bs = wtype == CLLM_TYPE_Q8_0 ? 34 : wtype == CLLM_TYPE_Q4_1 ? 20 : 18;
-    if (K % 32 || ((K / 32) * bs) % 4 || pro < 1 || pro > 4 || nrows <= 0 || nrows % 8 || ((uintptr_t) W & 3) || (uint64_t) nrows * (uint64_t)(K / 32 * bs) >= (1ull << 32)) return CLLM_E_UNSUPPORTED;
-    if (K > gemv_k_max(pro) || K < 256) return CLLM_E_UNSUPPORTED;
+    if (!mode || epi != 0 || wtype == CLLM_TYPE_Q4_K || ((uintptr_t) W & 3) || !gemv_row_shape_ok(wtype, K, nrows, pro, epi, bias, resid)) return CLLM_E_UNSUPPORTED;
+    if (nrows % 8 || K < 256) return CLLM_E_UNSUPPORTED;
     const int nblk = (int)(K / 32), cus = device_cu_count();
     const int nunits = (int)(nrows / 8);
     // teams per workgroup = units per CU (each team takes ONE unit at a time; more than 4 units per CU: the other kernels have enough rows)
@@ -403,23 +398,13 @@ int launch_gemv_team32(hipStream_t st, int wtype, const void * W, int64_t K, int
     if (!team || (nblk + 7) / 8 < team - 1) return CLLM_E_UNSUPPORTED;      // (a unit has at least one step per emit wave)
     const int nteams = 16 / team;
     int grid = (nunits + nteams - 1) / nteams; if (grid > cus) grid = cus;
-    const size_t lds = act_row_bytes(K, wtype == CLLM_TYPE_Q4_1 ? ACT_Q8_1 : ACT_Q8_0) + (wtype == CLLM_TYPE_Q4_0 ? (size_t) K : 0) + 32 * (size_t) T32_SLOT_BYTES;
-    if (lds > 158 * 1024) return CLLM_E_UNSUPPORTED;
+    const size_t lds = gemv_row_lds(wtype, K, wtype == CLLM_TYPE_Q4_0, 32 * (size_t) T32_SLOT_BYTES);
+    if (lds > K_GEMV_TEAM32_MAX_DYN_LDS) return CLLM_E_UNSUPPORTED;
     unsigned * g_t32_err = nullptr;
     { const int erc = kernel_error_word(&g_t32_err); if (erc) return erc; }
-    const int npre = gemv_npre(K);
-#define GOT(FMT_, PRO_, NPRE_) do { \
-        static uint64_t attr = 0; \
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_team32<FMT_, PRO_, NPRE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024)); dev_flag_set(attr); } \
-        hipLaunchKernelGGL((k_gemv_team32<FMT_, PRO_, NPRE_>), dim3((unsigned) grid), dim3(1024), lds, st, px, pw, (const char *) W, nblk, nunits, eps, dst, bias, resid, team, g_t32_err, g_t32_ts); } while (0)
-#define GOP(FMT_) do { \
-        if (pro == 1)      { if (npre == 1) GOT(FMT_, 1, 1); else GOT(FMT_, 1, 4); } \
-        else if (pro == 2) { if (npre == 1) GOT(FMT_, 2, 1); else if (npre == 4) GOT(FMT_, 2, 4); else GOT(FMT_, 2, 8); } \
-        else if (pro == 4) { if (npre == 1) GOT(FMT_, 4, 1); else if (npre == 4) GOT(FMT_, 4, 4); else GOT(FMT_, 4, 8); } \
-        else               { if (npre == 1) GOT(FMT_, 3, 1); else GOT(FMT_, 3, 4); } } while (0)
-    if (wtype == CLLM_TYPE_Q4_0) GOP(CLLM_TYPE_Q4_0); else if (wtype == CLLM_TYPE_Q4_1) GOP(CLLM_TYPE_Q4_1); else GOP(CLLM_TYPE_Q8_0);
-#undef GOP
-#undef GOT
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    return gemv_row_by_type32(wtype, [&](auto fmt) {
+        return gemv_row_by_pro_npre(pro, gemv_npre(K), [&](auto pro_c, auto npre_c) {
+            return gemv_row_launch<k_gemv_team32<decltype(fmt)::value, decltype(pro_c)::value, decltype(npre_c)::value>, K_GEMV_TEAM32_MAX_DYN_LDS>(st, grid, lds, px, pw, (const char *) W, nblk, nunits, eps, dst, bias, resid, team, g_t32_err, g_t32_ts);
+        });
+    });
 }

@@ -4,6 +4,8 @@ import os
 import re
 import subprocess
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -84,6 +86,15 @@ def test_kernels_with_hand_issued_loads_do_not_spill():
     err = _resource_usage("gemv_team32.hip")
     spills = re.findall(r"VGPRs Spill: (\d+)", err) + re.findall(r"SGPRs Spill: (\d+)", err) + re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)
     assert len(spills) >= 3 * 30 and all(int(x) == 0 for x in spills), sorted(set(spills))
+
+
+@pytest.mark.parametrize("name,kernels", [("gemv_rows.hip", 28), ("gemv_rows32.hip", 84)])
+def test_the_row_streaming_mat_vec_kernels_do_not_spill(name, kernels):
+    """k_gemv_rows waits for its DMA by count and k_gemv_rows32 keeps a ring of weight loads in registers; both share their prologue with k_gemv_team32 (gemv_act.h): the
+    same bar for every instantiation -- no spilled SGPR or VGPR, no scratch"""
+    err = _resource_usage(name)
+    spills = re.findall(r"VGPRs Spill: (\d+)", err) + re.findall(r"SGPRs Spill: (\d+)", err) + re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)
+    assert len(spills) >= 3 * kernels and all(int(x) == 0 for x in spills), sorted(set(spills))
 
 
 def test_the_decode_mat_vec_kernels_use_no_scratch():

@@ -994,6 +994,102 @@ def test_k_gemv_dec_leaf_equals_the_node_sequence(gpu, rows32_mode, team32_mode,
     assert np.array_equal(out.numpy().reshape(-1).view(np.uint32), want.view(np.uint32))
 
 
+# ---- the (PRO, EPI, NPRE, RPW) leaves of the three row-streaming kernels (gemv_rows.hip, gemv_rows32.hip, gemv_team32.hip) that no other test launches
+#      (profiles/gemv_row_kernels_shared.txt): each against the node sequence through k_gemv_dec
+#      A launcher that refuses hands the launch to k_gemv_dec without a word, and these cases would then pass on k_gemv_dec alone (as their neighbours above would): that they
+#      reach the named leaves is what the kernel trace in that profile shows, so a change to a pick, a threshold or a refusal calls for the trace to be made again.
+def _row_leaf_want(gpu, t, ws, K, pro, epi, x, g):
+    """the node sequence over the matrix ws (few rows: k_gemv_dec takes its mat-vec), before the residual: [RMS_NORM * weight | SiLU * up |] MUL_MAT [SiLU(gate) * up]"""
+    ops, T = gpu.ops, gpu.Tensor
+    U = ws.shape[0]
+    act = ops.rms_norm_mul(x, T.from_numpy(g.numpy().reshape(K)), 1e-5) if pro == 1 else x if pro == 2 else ops.silu_mul(x, g)      # (pro 3: the same values, interleaved below)
+    y = ops.mul_mat(T.from_numpy(ws, t, [K, U]), act)
+    if epi == 1:
+        y = y.numpy().reshape(U // 2, 2)
+        gate, up = (T.from_numpy(np.ascontiguousarray(y[:, i]).reshape(1, U // 2)) for i in range(2))
+        y = ops.mul(ops.silu(gate), up)
+    return y.numpy().reshape(-1)
+
+
+def _row_leaf_got(gpu, t, w, K, N, pro, epi, x, g, r):
+    """the one fused launch (pro 3, interleaved (gate_e, up_e) pairs, has no operator: cllm_bench_gemv_fused launches it, once before and once inside its timed region)"""
+    T, L = gpu.Tensor, gpu.lib.get()
+    out = T(gpu.F32, [N // 2 if epi == 1 else N, 1])
+    if pro == 3:
+        xgu = T.from_numpy(np.ascontiguousarray(np.stack([x.numpy().reshape(K), g.numpy().reshape(K)], axis=1)).reshape(1, 2 * K))
+        ptrs, us = (C.c_void_p * 1)(w.data_ptr().value), C.c_float()
+        gpu.lib.check(L.cllm_bench_gemv_fused(None, t, ptrs, 1, K, N, 3, xgu.data_ptr(), None, 1e-5, 0, out.data_ptr(), r.data_ptr(), 1, C.byref(us)), "bench_gemv_fused")
+    else:
+        cw = w.c()
+        gpu.lib.check(L.cllm_op_mul_mat_vec_fused(None, C.byref(cw), pro, x.data_ptr(), g.data_ptr() if pro != 2 else None, 1e-5, epi,
+                                                   None if epi == 1 else r.data_ptr(), out.data_ptr()), "fused")
+    return out.numpy().reshape(-1)
+
+
+# k_gemv_rows (Q4_K) has no setter and takes a launch only from 32 units of 8 rows per CU on, so N = 256 CUs + 8 (8 rows per wave; + 16 for whole gate / up pairs of a unit)
+# or + 4 (N % 8 != 0: 4 rows per wave, which needs K % 1024 == 0); one K per NPRE, the smallest the RPW takes.  The matrix repeats 320 random rows (160 gate / up pairs: a multiple of 8, so
+# the reference's SiLU node has no libm tail, as over the full count): the reference runs on those alone, through k_gemv_dec.  Not reachable from here: the arg-max epilogue (the decoder's lm_head only; test_gpu_llama.py launches (1, 2, 1, 8)) and the
+# SiLU(gate) * up epilogue at 4 rows per wave (whole pairs make N % 8 == 0, which picks 8).
+_ROWS_K = {(8, 1): 512, (8, 4): 4608, (8, 8): 16896, (4, 1): 1024, (4, 4): 5120, (4, 8): 17408}
+_ROWS_LEAVES = [(1, 0, 1, 8), (1, 0, 4, 8), (1, 1, 1, 8), (1, 1, 4, 8), (2, 0, 4, 8), (2, 0, 8, 8), (4, 0, 1, 8), (4, 0, 4, 8), (4, 0, 8, 8), (3, 0, 1, 8), (3, 0, 4, 8),
+                (1, 0, 1, 4), (1, 0, 4, 4), (2, 0, 1, 4), (2, 0, 4, 4), (2, 0, 8, 4), (4, 0, 1, 4), (4, 0, 4, 4), (4, 0, 8, 4), (3, 0, 1, 4), (3, 0, 4, 4)]
+
+
+@pytest.mark.parametrize("pro,epi,npre,rpw", _ROWS_LEAVES)
+def test_k_gemv_rows_leaf_equals_the_node_sequence(gpu, pro, epi, npre, rpw):
+    ops, T = gpu.ops, gpu.Tensor
+    n_cu = C.c_int(0)
+    gpu.lib.check(gpu.lib.get().cllm_device_info(0, None, 0, None, None, C.byref(n_cu)), "device_info")
+    K, U = _ROWS_K[(rpw, npre)], 320
+    N = 256 * n_cu.value + (4 if rpw == 4 else 16 if epi == 1 else 8)
+    ws = rand_blocks(O.Q4_K, U, K, rng)
+    x = T.from_numpy(rng.standard_normal((1, K)).astype(np.float32))
+    g = T.from_numpy((1 + 0.1 * rng.standard_normal((1, K))).astype(np.float32))
+    r = T.from_numpy(rng.standard_normal((1, N)).astype(np.float32))
+    ys = _row_leaf_want(gpu, O.Q4_K, ws, K, pro, epi, x, g)
+    if epi == 1:
+        want = ys[np.arange(N // 2) % (U // 2)]
+    else:
+        want = ops.add(T.from_numpy(ys[np.arange(N) % U].reshape(1, N)), r).numpy().reshape(-1)
+    w = T.from_numpy(ws[np.arange(N) % U], O.Q4_K, [K, N])
+    got = _row_leaf_got(gpu, O.Q4_K, w, K, N, pro, epi, x, g, r)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+# k_gemv_rows32 / k_gemv_team32: the debug setters force the form at any row count.  One K per NPRE: two blocks (rows are whole dwords), 4352, 16640; 80 rows = 10 units of 8.
+# k_gemv_team32 needs a step of 8 blocks per emit wave: K 1024 is four steps, teams of 4 and 5 waves.
+_R32_LEAVES = [(1, 1, 4, 8), (1, 1, 4, 2), (1, 1, 4, 4)] + [(pro, 0, npre, rpw) for pro, npre in ((4, 1), (4, 4), (4, 8), (3, 1), (3, 4)) for rpw in (2, 4)]
+_T32_LEAVES = [(4, 1), (3, 1), (3, 4)]
+
+
+def _row32_leaf(gpu, rows32_mode, team32_mode, modes, t, K, N, pro, epi):
+    ops, T = gpu.ops, gpu.Tensor
+    ws = rand_blocks(t, N, K, rng)
+    x = T.from_numpy(rng.standard_normal((1, K)).astype(np.float32))
+    g = T.from_numpy((1 + 0.1 * rng.standard_normal((1, K))).astype(np.float32))
+    r = T.from_numpy(rng.standard_normal((1, N)).astype(np.float32))
+    rows32_mode(0); team32_mode(0)
+    want = _row_leaf_want(gpu, t, ws, K, pro, epi, x, g)
+    if epi != 1:
+        want = ops.add(T.from_numpy(want.reshape(1, N)), r).numpy().reshape(-1)
+    rows32_mode(modes[0]); team32_mode(modes[1])
+    got = _row_leaf_got(gpu, t, T.from_numpy(ws, t, [K, N]), K, N, pro, epi, x, g, r)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("t", [O.Q4_0, O.Q4_1, O.Q8_0])
+@pytest.mark.parametrize("pro,epi,npre,rpw", _R32_LEAVES)
+def test_k_gemv_rows32_leaf_equals_the_node_sequence(gpu, rows32_mode, team32_mode, t, pro, epi, npre, rpw):
+    _row32_leaf(gpu, rows32_mode, team32_mode, (rpw, 0), t, {1: 64, 4: 4352, 8: 16640}[npre], 80, pro, epi)
+
+
+@pytest.mark.parametrize("t", [O.Q4_0, O.Q4_1, O.Q8_0])
+@pytest.mark.parametrize("team", [4, 5])
+@pytest.mark.parametrize("pro,npre", _T32_LEAVES)
+def test_k_gemv_team32_leaf_equals_the_node_sequence(gpu, rows32_mode, team32_mode, t, team, pro, npre):
+    _row32_leaf(gpu, rows32_mode, team32_mode, (0, team), t, {1: 1024, 4: 4352}[npre], 80, pro, 0)
+
+
 # ---- the tensor-parallel leaves (gemv_tp.hip) on two virtual ranks of one stream (cllm_tp_fused_create_group): the same K per NPRE and the same row counts as above
 _TYPES4 = [O.Q4_K, O.Q4_0, O.Q4_1, O.Q8_0]
 _DEC_K = {1: lambda t: 256 if t == O.Q4_K else 32, 4: lambda t: 4352, 8: lambda t: 16640}
