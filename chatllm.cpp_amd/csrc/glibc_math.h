@@ -4,6 +4,8 @@
 // sysdeps/ieee754/flt-32/{e_expf.c, s_sinf.c, s_cosf.c, sincosf.h} (ARM optimized routines): everything is evaluated in double and
 // rounded once to float, so only the operations' order matters, not the instruction selection.  Compiles for the host too:
 // oracle/glibc_math_check.c compares it with the libm of this image over the float range (tests/test_oracle_vs_reference.py).
+// Further down: tanhf / expm1f (float arithmetic, see there), the sigmoid expression, the fp32 <-> fp16 conversions and the two GELU tables
+// of the element-wise activations (tests/test_unary_model.py compares them with the reference's CPU backend).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -161,3 +163,154 @@ GM_FN float gm_sincosf(float y, int which) {
 }
 GM_FN float gm_sinf(float y) { return gm_sincosf(y, 0); }
 GM_FN float gm_cosf(float y) { return gm_sincosf(y, 1); }
+
+// ---- tanhf (s_tanhf.c) over expm1f (s_expm1f.c): the fdlibm float routines glibc 2.35 still ships -------------------------------------
+// Unlike expf above these are evaluated in FLOAT, every operation rounded on its own: the unit must be compiled without contraction
+// (-ffp-contract=off), as glibc itself is, and the divisions are IEEE.  UNARY(TANH) (unary-ops.cpp:19-21) and the tanhf inside
+// ggml_gelu_f32 (vec.h:976-978) call it.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GM_DIV(a, b) __fdiv_rn((a), (b))
+#else
+#define GM_DIV(a, b) ((a) / (b))
+#endif
+GM_FN float gm_expm1f(float x) {
+    const float one = 1.0f, huge = 1.0e+30f, tiny = 1.0e-30f;
+    const float o_threshold = 8.8721679688e+01f, ln2_hi = 6.9313812256e-01f, ln2_lo = 9.0580006145e-06f, invln2 = 1.4426950216e+00f;
+    const float Q1 = -3.3333335072e-02f, Q2 = 1.5873016091e-03f, Q3 = -7.9365076090e-05f, Q4 = 4.0082177293e-06f, Q5 = -2.0109921195e-07f;
+    float y, hi, lo, c = 0.0f, t, e, hxs, hfx, r1;
+    int32_t k;
+    uint32_t hx = gm_asuint(x);
+    const uint32_t xsb = hx & 0x80000000u;                  // sign bit of x
+    hx &= 0x7fffffffu;
+    if (hx >= 0x4195b844u) {                                // |x| >= 27 ln2
+        if (hx >= 0x42b17218u) {                            // |x| >= 88.721...
+            if (hx > 0x7f800000u) return x + x;             // nan
+            if (hx == 0x7f800000u) return xsb == 0 ? x : -1.0f;
+            if (x > o_threshold) return gm_asfloat(0x7f800000u);                // huge * huge
+        }
+        if (xsb != 0) return tiny - one;                    // x < -27 ln2: -1
+    }
+    if (hx > 0x3eb17218u) {                                 // |x| > 0.5 ln2
+        if (hx < 0x3F851592u) {                             // and |x| < 1.5 ln2
+            if (xsb == 0) { hi = x - ln2_hi; lo =  ln2_lo; k =  1; }
+            else          { hi = x + ln2_hi; lo = -ln2_lo; k = -1; }
+        } else {
+            k = (int32_t)(invln2 * x + (xsb == 0 ? 0.5f : -0.5f));
+            t = (float) k;
+            hi = x - t * ln2_hi;                            // t * ln2_hi is exact here
+            lo = t * ln2_lo;
+        }
+        x = hi - lo;
+        c = (hi - x) - lo;
+    } else if (hx < 0x33000000u) {                          // |x| < 2^-25: x
+        t = huge + x;
+        return x - (t - (huge + x));
+    } else k = 0;
+    hfx = 0.5f * x;
+    hxs = x * hfx;
+    r1 = one + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
+    t = 3.0f - r1 * hfx;
+    e = hxs * GM_DIV(r1 - t, 6.0f - x * t);
+    if (k == 0) return x - (x * e - hxs);                   // c is 0
+    e = (x * (e - c) - c);
+    e -= hxs;
+    if (k == -1) return 0.5f * (x - e) - 0.5f;
+    if (k == 1) {
+        if (x < -0.25f) return -2.0f * (e - (x + 0.5f));
+        return one + 2.0f * (x - e);
+    }
+    if (k <= -2 || k > 56) {                                // suffice to return exp(x) - 1
+        y = one - (e - x);
+        y = gm_asfloat(gm_asuint(y) + ((uint32_t) k << 23));                    // add k to y's exponent
+        return y - one;
+    }
+    if (k < 23) {
+        t = gm_asfloat(0x3f800000u - (0x1000000u >> k));    // 1 - 2^-k
+        y = t - (e - x);
+        y = gm_asfloat(gm_asuint(y) + ((uint32_t) k << 23));
+    } else {
+        t = gm_asfloat((uint32_t)(0x7f - k) << 23);         // 2^-k
+        y = x - (e + t);
+        y += one;
+        y = gm_asfloat(gm_asuint(y) + ((uint32_t) k << 23));
+    }
+    return y;
+}
+GM_FN float gm_tanhf(float x) {
+    const float one = 1.0f, two = 2.0f, tiny = 1.0e-30f;
+    float t, z;
+    const uint32_t jx = gm_asuint(x), ix = jx & 0x7fffffffu;
+    if (ix >= 0x7f800000u) {
+        if (ix > 0x7f800000u) return gm_asfloat(jx | 0x00400000u);             // one / x +- one on a nan: the nan itself, quiet (its sign and payload kept)
+        return (jx >> 31) ? -one : one;                     // one / x +- one on +-inf
+    }
+    if (ix < 0x41b00000u) {                                 // |x| < 22
+        if (ix == 0) return x;                              // +-0
+        if (ix < 0x24000000u) return x * (one + x);         // |x| < 2^-55
+        if (ix >= 0x3f800000u) {                            // |x| >= 1
+            t = gm_expm1f(two * __builtin_fabsf(x));
+            z = one - GM_DIV(two, t + two);
+        } else {
+            t = gm_expm1f(-two * __builtin_fabsf(x));
+            z = GM_DIV(-t, t + two);
+        }
+    } else z = one - tiny;                                  // |x| >= 22: +-1
+    return (jx >> 31) ? -z : z;
+}
+
+// ---- UNARY(SIGMOID): op_sigmoid, unary-ops.cpp:31-33: 1.f / (1.f + expf(-x)), libm expf per element, IEEE division ---------------------
+GM_FN float gm_sigmoidf(float x) {
+    if (x != x) return gm_asfloat((gm_asuint(x) ^ 0x80000000u) | 0x00400000u);  // the nan of -x, made quiet by expf's x + x, through + and / unchanged
+    return GM_DIV(1.0f, 1.0f + gm_expf(-x));
+}
+
+// ---- fp32 <-> fp16 as the reference's x86-64-v3 build converts single values: GGML_CPU_FP32_TO_FP16 is NOT F16C there but the portable
+// ggml_compute_fp32_to_fp16 (simd-mappings.h:143-145 -> ggml-impl.h:401-425: round to nearest even, every nan -> sign | 0x7e00), and
+// GGML_CPU_FP16_TO_FP32 a lookup in ggml_table_f32_f16, filled by ggml_compute_fp16_to_fp32 (ggml-impl.h:378-399: exact; its float
+// multiply turns a signalling nan quiet).  In integers here, so that host and device cannot differ.
+GM_FN uint16_t gm_fp32_to_fp16(float f) {
+    const uint32_t u = gm_asuint(f), a = u & 0x7fffffffu;
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                    // >= 65520 (the tie above the largest half goes to the even side: inf), inf
+    uint32_t r, rem, half;
+    if (a < 0x38800000u) {                                  // below the smallest normal half (2^-14): r = RNE(|f| * 2^24)
+        if (a < 0x33000000u) return sign;                   // < 2^-25
+        const uint32_t shift = 126u - (a >> 23), m = (a & 0x7fffffu) | 0x800000u;                  // 14 .. 24
+        r = m >> shift; rem = m & ((1u << shift) - 1u); half = 1u << (shift - 1u);
+    } else {
+        r = (a - 0x38000000u) >> 13; rem = a & 0x1fffu; half = 0x1000u;                            // (a carry out of the mantissa steps the exponent)
+    }
+    if (rem > half || (rem == half && (r & 1u))) r++;
+    return (uint16_t)(sign | r);
+}
+GM_FN float gm_fp16_to_fp32(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
+    if (e == 0x1fu) return gm_asfloat(sign | 0x7f800000u | (m << 13) | (m ? 0x00400000u : 0u));
+    if (e == 0u) return gm_asfloat(sign | gm_asuint((float)(int32_t) m * 0x1p-24f));               // zero and the subnormal halves: m * 2^-24, exact
+    return gm_asfloat(sign | ((e + 112u) << 23) | (m << 13));
+}
+
+// ---- UNARY(GELU) / UNARY(GELU_QUICK) with GGML_GELU_FP16 / GGML_GELU_QUICK_FP16 (vec.h:17-18, the default build): a 65 536-entry fp16 table
+// indexed by the fp16 rounding of x (ggml_vec_gelu_f32, vec.h:996-1009; ggml_vec_gelu_quick_f32, vec.h:1037-1044), filled by ggml_cpu_init
+// (ggml-cpu.c:3694-3703) from ggml_gelu_f32 (vec.h:976-978) and ggml_gelu_quick_f32 (vec.h:1025-1027) with the host's tanhf / expf -- here
+// with their restatements above, in float and uncontracted as that C11 unit is compiled.  Host side only: the device loads the tables.
+GM_FN float gm_gelu_lookup(const uint16_t * tab /* gelu */, float x) {
+    return x <= -10.0f ? 0.0f : x >= 10.0f ? x : gm_fp16_to_fp32(tab[gm_fp32_to_fp16(x)]);          // (a nan fails both tests: the table's nan entries)
+}
+GM_FN float gm_gelu_quick_lookup(const uint16_t * tab /* gelu_quick */, float x) { return gm_fp16_to_fp32(tab[gm_fp32_to_fp16(x)]); }      // no clamp: +-inf entries included
+static inline float gm_gelu_f32(float x) {
+    const float GELU_COEF_A = 0.044715f, SQRT_2_OVER_PI = 0.79788456080286535587989211986876f;
+    return 0.5f * x * (1.0f + gm_tanhf(SQRT_2_OVER_PI * x * (1.0f + GELU_COEF_A * x * x)));
+}
+static inline float gm_gelu_quick_f32(float x) {
+    const float GELU_QUICK_COEF = -1.702f;
+    return x * (1.0f / (1.0f + gm_expf(GELU_QUICK_COEF * x)));
+}
+static inline void gm_build_gelu_tables(uint16_t * gelu /* [65536] */, uint16_t * gelu_quick /* [65536] */) {
+    for (uint32_t i = 0; i < 65536u; i++) {
+        const float f = gm_fp16_to_fp32((uint16_t) i);
+        gelu[i]       = gm_fp32_to_fp16(gm_gelu_f32(f));
+        gelu_quick[i] = gm_fp32_to_fp16(gm_gelu_quick_f32(f));
+    }
+}

@@ -5,6 +5,8 @@
 #include "quant_dev.h"
 
 #include <math.h>
+#include <mutex>
+#include <vector>
 
 // ================================================================================================
 // RMS_NORM (+ MUL)      ggml_compute_forward_rms_norm_f32, ggml-cpu/ops.cpp:3710-3759
@@ -421,7 +423,22 @@ extern "C" int cllm_op_scale_mask_soft_max(void * stream, const cllm_tensor * sr
 // ================================================================================================
 // element-wise family: generic strided, one thread per element of dst, index decomposed over ne[]
 // ================================================================================================
-enum { EW_DIAG_MASK = 0, EW_SCALE = 1, EW_SILU = 2, EW_ADD = 3, EW_MUL = 4, EW_SILU_MUL = 5, EW_DIV = 6 };
+enum { EW_DIAG_MASK = 0, EW_SCALE = 1, EW_SILU = 2, EW_ADD = 3, EW_MUL = 4, EW_SILU_MUL = 5, EW_DIV = 6,
+       EW_SIGMOID = 7, EW_TANH = 8, EW_RELU = 9, EW_SQR = 10, EW_GELU = 11, EW_GELU_QUICK = 12 };
+
+// ggml_table_gelu_f16 / ggml_table_gelu_quick_f16 (vec.cpp:5-9), built on the host by gm_build_gelu_tables and uploaded once per device
+__device__ uint16_t g_gelu_tab[2][1 << 16];
+static int gelu_tables_upload() {
+    static std::mutex m;
+    static uint64_t up = 0;
+    static std::vector<uint16_t> tab;
+    std::lock_guard<std::mutex> lock(m);
+    if (!dev_flag_unset(up)) return CLLM_OK;
+    if (tab.empty()) { tab.resize(2 << 16); gm_build_gelu_tables(tab.data(), tab.data() + (1 << 16)); }
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_gelu_tab), tab.data(), tab.size() * sizeof(uint16_t)));
+    dev_flag_set(up);
+    return CLLM_OK;
+}
 
 template <int OP>
 __global__ void __launch_bounds__(256) k_elementwise(tview a, tview b, tview d, float f0, float f1, int i0p) {
@@ -438,7 +455,14 @@ __global__ void __launch_bounds__(256) k_elementwise(tview a, tview b, tview d, 
         else if (OP == EW_SILU) {
             // ggml_vec_silu_f32 (vec.cpp:396-431): AVX2 body for i0 < (ne0 & ~7), scalar expf tail
             y = (i0 < (d.ne[0] & ~(int64_t) 7)) ? x / (1.0f + ggml_expf_poly(0.0f - x)) : x / (1.0f + libm_expf(-x));
-        } else {
+        }
+        else if (OP == EW_SIGMOID)   y = gm_sigmoidf(x);                                 // op_sigmoid (unary-ops.cpp:31-33): no vector body, libm expf
+        else if (OP == EW_TANH)      y = gm_tanhf(x);                                    // op_tanh (unary-ops.cpp:19-21): libm tanhf
+        else if (OP == EW_RELU)      y = (x > 0.0f) ? x : 0.0f;                          // op_relu (unary-ops.cpp:27-29)
+        else if (OP == EW_SQR)       y = x * x;                                          // op_sqr (unary-ops.cpp:47-49)
+        else if (OP == EW_GELU)      y = gm_gelu_lookup(g_gelu_tab[0], x);                 // ggml_vec_gelu_f32 (vec.h:996-1009)
+        else if (OP == EW_GELU_QUICK) y = gm_gelu_quick_lookup(g_gelu_tab[1], x);          // ggml_vec_gelu_quick_f32 (vec.h:1037-1044)
+        else {
             const float z = *(const float *)(b.data + (i0 % b.ne[0])*b.nb[0] + (i1 % b.ne[1])*b.nb[1] + (i2 % b.ne[2])*b.nb[2] + (i3 % b.ne[3])*b.nb[3]);
             if (OP == EW_ADD)      y = x + z;
             else if (OP == EW_MUL) y = x * z;
@@ -472,9 +496,21 @@ extern "C" int cllm_op_diag_mask_inf(void * stream, const cllm_tensor * src, cll
 }
 extern "C" int cllm_op_scale(void * stream, const cllm_tensor * src, cllm_tensor * dst, float s, float b) { return ew_launch<EW_SCALE>(stream, src, nullptr, dst, s, b, 0, "scale"); }
 extern "C" int cllm_op_unary(void * stream, int op, const cllm_tensor * src, cllm_tensor * dst) {
-    if (op != CLLM_UNARY_SILU) FAIL(CLLM_E_UNSUPPORTED, "unary: op %d", op);
+    if (op != CLLM_UNARY_SILU && op != CLLM_UNARY_TANH && op != CLLM_UNARY_RELU && op != CLLM_UNARY_SIGMOID && op != CLLM_UNARY_GELU && op != CLLM_UNARY_GELU_QUICK)
+        FAIL(CLLM_E_UNSUPPORTED, "unary: op %d", op);
     if (src && dst && (src->nb[0] != 4 || dst->nb[0] != 4)) FAIL(CLLM_E_UNSUPPORTED, "unary: rows must be dense");
-    return ew_launch<EW_SILU>(stream, src, nullptr, dst, 0, 0, 0, "silu");
+    switch (op) {
+        case CLLM_UNARY_TANH:    return ew_launch<EW_TANH>(stream, src, nullptr, dst, 0, 0, 0, "tanh");
+        case CLLM_UNARY_RELU:    return ew_launch<EW_RELU>(stream, src, nullptr, dst, 0, 0, 0, "relu");
+        case CLLM_UNARY_SIGMOID: return ew_launch<EW_SIGMOID>(stream, src, nullptr, dst, 0, 0, 0, "sigmoid");
+        case CLLM_UNARY_GELU:       if (int rc = gelu_tables_upload()) return rc; return ew_launch<EW_GELU>(stream, src, nullptr, dst, 0, 0, 0, "gelu");
+        case CLLM_UNARY_GELU_QUICK: if (int rc = gelu_tables_upload()) return rc; return ew_launch<EW_GELU_QUICK>(stream, src, nullptr, dst, 0, 0, 0, "gelu_quick");
+        default:                 return ew_launch<EW_SILU>(stream, src, nullptr, dst, 0, 0, 0, "silu");
+    }
+}
+extern "C" int cllm_op_sqr(void * stream, const cllm_tensor * src, cllm_tensor * dst) {
+    if (src && dst && (src->nb[0] != 4 || dst->nb[0] != 4)) FAIL(CLLM_E_UNSUPPORTED, "sqr: rows must be dense");
+    return ew_launch<EW_SQR>(stream, src, nullptr, dst, 0, 0, 0, "sqr");
 }
 extern "C" int cllm_op_add(void * stream, const cllm_tensor * a, const cllm_tensor * b, cllm_tensor * dst) { if (!b) FAIL(CLLM_E_INVALID, "add: null"); return ew_launch<EW_ADD>(stream, a, b, dst, 0, 0, 0, "add"); }
 extern "C" int cllm_op_mul(void * stream, const cllm_tensor * a, const cllm_tensor * b, cllm_tensor * dst) { if (!b) FAIL(CLLM_E_INVALID, "mul: null"); return ew_launch<EW_MUL>(stream, a, b, dst, 0, 0, 0, "mul"); }

@@ -408,7 +408,12 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
         case GGML_OP_SUM_ROWS: return f32_dense(a) && f32_dense(op);
         case GGML_OP_TOP_K: return f32_dense(a) && op->type == GGML_TYPE_I32 && a->ne[0] <= 4096;
         case GGML_OP_SCALE: case GGML_OP_DIAG_MASK_INF: return a->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32;
-        case GGML_OP_UNARY: return ggml_get_unary_op(op) == GGML_UNARY_OP_SILU && f32_dense(a) && f32_dense(op);
+        case GGML_OP_UNARY: switch (ggml_get_unary_op(op)) {      // the codes of cllm_unary (ggml::act's nodes, src/layers.cpp:441-485)
+            case GGML_UNARY_OP_SILU: case GGML_UNARY_OP_TANH: case GGML_UNARY_OP_RELU: case GGML_UNARY_OP_SIGMOID: case GGML_UNARY_OP_GELU: case GGML_UNARY_OP_GELU_QUICK:
+                return f32_dense(a) && f32_dense(op);
+            default: return false;
+        }
+        case GGML_OP_SQR: return f32_dense(a) && f32_dense(op);
         case GGML_OP_ROPE: {
             const int mode = op->op_params[2];
             return f32_dense(a) && f32_dense(op) && b && b->type == GGML_TYPE_I32 && (mode == 0 || mode == 2) && (!op->src[2] || op->src[2]->type == GGML_TYPE_F32);
@@ -2155,7 +2160,8 @@ ggml_status be_graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
             } else rc = CALL(cllm_op_top_k, st, &da, &d); break;
             case GGML_OP_SCALE: { float s, bias; memcpy(&s, n->op_params, 4); memcpy(&bias, (const float *) n->op_params + 1, 4); rc = CALL(cllm_op_scale, st, &da, &d, s, bias); } break;
             case GGML_OP_DIAG_MASK_INF: rc = CALL(cllm_op_diag_mask_inf, st, &da, &d, n->op_params[0]); break;
-            case GGML_OP_UNARY: rc = CALL(cllm_op_unary, st, CLLM_UNARY_SILU, &da, &d); break;
+            case GGML_OP_UNARY: rc = CALL(cllm_op_unary, st, (int) ggml_get_unary_op(n), &da, &d); break;      // cllm_unary == ggml_unary_op
+            case GGML_OP_SQR: rc = CALL(cllm_op_sqr, st, &da, &d); break;
             case GGML_OP_ROPE: {
                 cllm_rope_params p;
                 p.n_dims = n->op_params[1]; p.mode = n->op_params[2]; p.n_ctx_orig = n->op_params[4];

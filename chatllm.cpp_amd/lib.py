@@ -118,6 +118,7 @@ SIGNATURES = {
     "cllm_attn_decode_wsize": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64]),
     "cllm_op_rope_kv_attn_decode": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64, _P, _P, C.c_size_t]),
     "cllm_op_unary": (C.c_int, [_P, C.c_int, _T, _T]),
+    "cllm_op_sqr": (C.c_int, [_P, _T, _T]),
     "cllm_op_add": (C.c_int, [_P, _T, _T, _T]),
     "cllm_op_mul": (C.c_int, [_P, _T, _T, _T]),
     "cllm_op_div": (C.c_int, [_P, _T, _T, _T]),

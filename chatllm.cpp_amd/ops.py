@@ -9,7 +9,7 @@ from . import lib as _l
 from .tensor import Tensor, F32, F16, I32, I64, Buffer  # noqa: F401
 
 ROPE_NORMAL, ROPE_NEOX = 0, 2
-UNARY_SILU = 10
+UNARY_TANH, UNARY_RELU, UNARY_SIGMOID, UNARY_GELU, UNARY_GELU_QUICK, UNARY_SILU = 4, 6, 7, 8, 9, 10      # == enum ggml_unary_op
 
 _wdata = {"buf": None}
 
@@ -156,9 +156,41 @@ def rope_kv_attn_decode(qkv, pos, n_kv, n_head, n_kv_head, head_dim, rope_mode, 
     return dst
 
 
-def silu(a, dst=None):
+def unary(op, a, dst=None):
+    """ggml::act's nodes (src/layers.cpp:441-485): UNARY(op) of a dense F32 tensor; dst may be a itself (the `_inplace` forms)"""
     dst = dst or Tensor(F32, a.ne)
-    _l.check(_l.get().cllm_op_unary(None, UNARY_SILU, _ref(a), _ref(dst)), "silu")
+    _l.check(_l.get().cllm_op_unary(None, op, _ref(a), _ref(dst)), f"unary({op})")
+    return dst
+
+
+def silu(a, dst=None):
+    return unary(UNARY_SILU, a, dst)
+
+
+def tanh(a, dst=None):
+    return unary(UNARY_TANH, a, dst)
+
+
+def relu(a, dst=None):
+    return unary(UNARY_RELU, a, dst)
+
+
+def sigmoid(a, dst=None):
+    return unary(UNARY_SIGMOID, a, dst)
+
+
+def gelu(a, dst=None):
+    return unary(UNARY_GELU, a, dst)
+
+
+def gelu_quick(a, dst=None):
+    return unary(UNARY_GELU_QUICK, a, dst)
+
+
+def sqr(a, dst=None):
+    """GGML_OP_SQR: the second node of RELU2"""
+    dst = dst or Tensor(F32, a.ne)
+    _l.check(_l.get().cllm_op_sqr(None, _ref(a), _ref(dst)), "sqr")
     return dst
 
 

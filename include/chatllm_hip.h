@@ -289,9 +289,21 @@ CLLM_API int    cllm_op_rope_kv_attn_decode(void * stream, const float * qkv, co
                                             int n_head, int n_kv_head, int head_dim, int rope_mode, void * k_cache, void * v_cache, int64_t max_len,
                                             float * out, void * wdata, size_t wsize);
 
-typedef enum cllm_unary { CLLM_UNARY_SILU = 10 /* == GGML_UNARY_OP_SILU */ } cllm_unary;
-/* GGML_OP_UNARY         ggml_vec_silu_f32 (ggml-cpu/vec.cpp:396-431) */
+/* numeric values == enum ggml_unary_op (ggml.h:579-604) */
+typedef enum cllm_unary {
+    CLLM_UNARY_TANH = 4, CLLM_UNARY_RELU = 6, CLLM_UNARY_SIGMOID = 7, CLLM_UNARY_GELU = 8, CLLM_UNARY_GELU_QUICK = 9, CLLM_UNARY_SILU = 10,
+} cllm_unary;
+/* GGML_OP_UNARY, F32 -> F32 with dense rows (nb[0] == 4), dst may be src; every op has the bits of the reference's x86-64-v3 CPU build, NaN payloads included:
+ *   SILU        ggml_vec_silu_f32 (ggml-cpu/vec.cpp:396-431)
+ *   TANH        op_tanh (ggml-cpu/unary-ops.cpp:19-21): libm tanhf per element
+ *   RELU        op_relu (ggml-cpu/unary-ops.cpp:27-29): (x > 0) ? x : 0
+ *   SIGMOID     op_sigmoid (ggml-cpu/unary-ops.cpp:31-33): 1 / (1 + expf(-x)), libm expf per element
+ *   GELU        ggml_vec_gelu_f32 (ggml-cpu/vec.h:996-1009): 0 at x <= -10, x at x >= 10, else ggml_table_gelu_f16[fp16(x)] (filled by ggml_cpu_init, ggml-cpu.c:3694-3703)
+ *   GELU_QUICK  ggml_vec_gelu_quick_f32 (ggml-cpu/vec.h:1037-1044): ggml_table_gelu_quick_f16[fp16(x)] for every x
+ * any other op, and GELU_ERF: CLLM_E_UNSUPPORTED */
 CLLM_API int cllm_op_unary(void * stream, int op, const cllm_tensor * src, cllm_tensor * dst);
+/* GGML_OP_SQR  op_sqr (ggml-cpu/unary-ops.cpp:47-49): x * x; the second node of RELU2 (ggml::act, src/layers.cpp:441-485).  Same tensor predicates as cllm_op_unary */
+CLLM_API int cllm_op_sqr(void * stream, const cllm_tensor * src, cllm_tensor * dst);
 /* GGML_OP_ADD / GGML_OP_MUL with broadcast of src1 (ggml-cpu/binary-ops.cpp) */
 CLLM_API int cllm_op_add(void * stream, const cllm_tensor * a, const cllm_tensor * b, cllm_tensor * dst);
 CLLM_API int cllm_op_mul(void * stream, const cllm_tensor * a, const cllm_tensor * b, cllm_tensor * dst);

@@ -1,0 +1,151 @@
+"""The reference's own CPU backend (oracle/_ref/libggml-cpu.so over libggml-base.so, built from the reference by oracle/Makefile) driven
+through its public ggml C API with ctypes: ggml_init, ggml_new_tensor_4d, the op constructor, ggml_build_forward_expand,
+ggml_graph_compute_with_ctx.  The oracle of the element-wise ops that oracle/ref_ops.c does not expose (TANH, RELU, SIGMOID, GELU,
+GELU_QUICK, SQR).  Also: the input sets the CPU and the GPU tests of these ops share."""
+import ctypes as C
+import os
+
+import numpy as np
+
+REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
+GGML_TYPE_F32 = 0
+# the codes of cllm_unary (== enum ggml_unary_op); SQR is an op of its own (GGML_OP_SQR)
+TANH, RELU, SIGMOID, GELU, GELU_QUICK, SQR = 4, 6, 7, 8, 9, -1
+OPS = {"tanh": TANH, "relu": RELU, "sigmoid": SIGMOID, "gelu": GELU, "gelu_quick": GELU_QUICK, "sqr": SQR}
+_CTOR = {TANH: "ggml_tanh", RELU: "ggml_relu", SIGMOID: "ggml_sigmoid", GELU: "ggml_gelu", GELU_QUICK: "ggml_gelu_quick", SQR: "ggml_sqr"}
+
+
+class _InitParams(C.Structure):
+    _fields_ = [("mem_size", C.c_size_t), ("mem_buffer", C.c_void_p), ("no_alloc", C.c_bool)]
+
+
+_libs = None
+
+
+def available():
+    return os.path.exists(os.path.join(REF, "libggml-base.so")) and os.path.exists(os.path.join(REF, "libggml-cpu.so"))
+
+
+def libs():
+    """(libggml-base, libggml-cpu) with the prototypes this file uses"""
+    global _libs
+    if _libs is None:
+        if not available():
+            raise RuntimeError(f"{REF}/libggml-cpu.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` where the reference lies")
+        base = C.CDLL(os.path.join(REF, "libggml-base.so"), mode=C.RTLD_GLOBAL)
+        cpu = C.CDLL(os.path.join(REF, "libggml-cpu.so"), mode=C.RTLD_GLOBAL)
+        P = C.c_void_p
+        base.ggml_init.restype, base.ggml_init.argtypes = P, [_InitParams]
+        base.ggml_free.restype, base.ggml_free.argtypes = None, [P]
+        base.ggml_new_tensor_4d.restype, base.ggml_new_tensor_4d.argtypes = P, [P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+        base.ggml_get_data.restype, base.ggml_get_data.argtypes = P, [P]
+        base.ggml_new_graph.restype, base.ggml_new_graph.argtypes = P, [P]
+        base.ggml_build_forward_expand.restype, base.ggml_build_forward_expand.argtypes = None, [P, P]
+        base.ggml_tensor_overhead.restype, base.ggml_graph_overhead.restype = C.c_size_t, C.c_size_t
+        for name in _CTOR.values():
+            getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P]
+        cpu.ggml_cpu_init.restype, cpu.ggml_cpu_init.argtypes = None, []
+        cpu.ggml_graph_compute_with_ctx.restype, cpu.ggml_graph_compute_with_ctx.argtypes = C.c_int, [P, P, C.c_int]
+        base.ggml_fp32_to_fp16_row.restype, base.ggml_fp32_to_fp16_row.argtypes = None, [P, P, C.c_int64]
+        base.ggml_fp16_to_fp32_row.restype, base.ggml_fp16_to_fp32_row.argtypes = None, [P, P, C.c_int64]
+        cpu.ggml_cpu_init()                 # fills ggml_table_gelu_f16 / ggml_table_gelu_quick_f16 (ggml-cpu.c:3694-3703)
+        _libs = (base, cpu)
+    return _libs
+
+
+def unary(op, x):
+    """the reference's result of one op node over x (float32, up to 4 dimensions, numpy order = reversed ne), same shape"""
+    base, cpu = libs()
+    x = np.ascontiguousarray(x, np.float32)
+    ne = list(reversed(x.shape)) + [1] * (4 - x.ndim)
+    mem = 2 * x.nbytes + 8 * base.ggml_tensor_overhead() + base.ggml_graph_overhead() + (1 << 16)
+    ctx = base.ggml_init(_InitParams(mem, None, False))
+    assert ctx
+    try:
+        a = base.ggml_new_tensor_4d(ctx, GGML_TYPE_F32, *ne)
+        C.memmove(base.ggml_get_data(a), x.ctypes.data, x.nbytes)
+        d = getattr(base, _CTOR[op])(ctx, a)
+        g = base.ggml_new_graph(ctx)
+        base.ggml_build_forward_expand(g, d)
+        assert cpu.ggml_graph_compute_with_ctx(ctx, g, 1) == 0
+        out = np.empty_like(x)
+        C.memmove(out.ctypes.data, base.ggml_get_data(d), x.nbytes)
+        return out
+    finally:
+        base.ggml_free(ctx)
+
+
+def gelu_tables():
+    """(ggml_table_gelu_f16, ggml_table_gelu_quick_f16) as the reference's ggml_cpu_init filled them: uint16 [65536] each"""
+    _, cpu = libs()
+    return tuple(np.ctypeslib.as_array((C.c_uint16 * 65536).in_dll(cpu, name)).copy() for name in ("ggml_table_gelu_f16", "ggml_table_gelu_quick_f16"))
+
+
+def fp32_to_fp16(x):
+    """ggml_fp32_to_fp16_row: the portable ggml_compute_fp32_to_fp16 (ggml-impl.h:401-425) per element -- what GGML_CPU_FP32_TO_FP16 is in the
+    x86-64-v3 build (simd-mappings.h:143-145) -- as uint16"""
+    base, _ = libs()
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty(x.size, np.uint16)
+    base.ggml_fp32_to_fp16_row(x.ctypes.data, y.ctypes.data, x.size)
+    return y
+
+
+def fp16_to_fp32(h):
+    """ggml_fp16_to_fp32_row: ggml_compute_fp16_to_fp32 (ggml-impl.h:378-399), which also fills ggml_table_f32_f16"""
+    base, _ = libs()
+    h = np.ascontiguousarray(h, np.uint16)
+    y = np.empty(h.size, np.float32)
+    base.ggml_fp16_to_fp32_row(h.ctypes.data, y.ctypes.data, h.size)
+    return y
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------------------
+def _f(bits):
+    return np.asarray(bits, np.uint32).view(np.float32)
+
+
+def special_values():
+    """+-0, +-inf, NaNs (quiet and signalling, either sign, payloads in the high and in the low mantissa bits), the smallest and largest
+    subnormals, +-FLT_MIN, +-FLT_MAX, the GELU clamp at +-10 and the fp16 range's edges: 65504, the tie at 65520, 2^-24, the tie at 2^-25"""
+    b = [0x00000000, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001, 0x7fa00000, 0xffa55aa5, 0x7fffffff, 0xffffffff,
+         0x7fc02000, 0x7f802000, 0x7fc01fff,
+         0x00000001, 0x80000001, 0x007fffff, 0x807fffff, 0x00800000, 0x80800000, 0x7f7fffff, 0xff7fffff]
+    v = [10.0, -10.0, 65504.0, 65519.996, 65520.0, -65520.0, 2.0 ** -24, 2.0 ** -25, -2.0 ** -25, 1.5 * 2.0 ** -25, 2.0 ** -14, 1.0, -1.0, 22.0, -22.0, 0.5, 88.0, -88.0, -104.0]
+    f = np.array(v, np.float32)
+    near = np.concatenate([np.nextafter(f, np.float32(np.inf)), np.nextafter(f, np.float32(-np.inf))])
+    return np.concatenate([_f(b), f, near])
+
+
+def threshold_neighbours():
+    """the neighbours (-2 .. +2 ulp, both signs) of every branch threshold of glibc's tanhf (s_tanhf.c: inf, 22, 1, 2^-55), of the expm1f it
+    calls on 2|x| and -2|x| (s_expm1f.c: 27 ln2, 88.72, 0.5 ln2, 1.5 ln2, 2^-25, and k = 23, 56 / 57 through x = k ln2; the thresholds
+    themselves and their halves, which is where tanhf's argument puts them) and of expf (e_expf.c: |x| >= 88, overflow, underflow,
+    may-underflow), which SIGMOID and GELU_QUICK call"""
+    t = [0x7f800000, 0x41b00000, 0x3f800000, 0x24000000,
+         0x4195b844, 0x42b17218, 0x42b17180, 0x3eb17218, 0x3f851592, 0x33000000]
+    t += [int(np.float32(k * np.log(2.0)).view(np.uint32)) for k in (2, 22, 23, 24, 56, 57, 58)]
+    t += [int(np.float32(k * np.log(2.0) + 0.5 * np.log(2.0)).view(np.uint32)) for k in (1, 2, 22, 23, 56, 57)]      # where k = (int)(x / ln2 + 0.5) steps
+    t += [b - 0x00800000 for b in list(t) if 0x00800000 < b < 0x7f800000]                    # halved: tanhf hands expm1f 2|x|
+    t += [0x42b00000] + [int(np.float32(float.fromhex(h)).view(np.uint32)) for h in ("0x1.62e42ep6", "0x1.9fe368p6", "0x1.9d1d9ep6")]      # expf: 88 and its three range tests
+    t += [int(np.float32(float.fromhex(h) / 1.702).view(np.uint32)) for h in ("0x1.62e42ep6", "0x1.9fe368p6", "0x1.9d1d9ep6")]             # the same, reached through GELU_QUICK's -1.702 x
+    bits = []
+    for b in t:
+        for d in range(-2, 3):
+            v = b + d
+            if 0 <= v <= 0x7fffffff:
+                bits += [v, v | 0x80000000]
+    return _f(bits)
+
+
+def all_fp16_values():
+    """every fp16-representable value as float32 (NaNs included): all 65 536 indices of the two GELU tables"""
+    return np.arange(65536, dtype=np.uint32).astype(np.uint16).view(np.float16).astype(np.float32)
+
+
+def random_bits(n=1 << 20, seed=20250607):
+    return np.random.default_rng(seed).integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32).view(np.float32)
+
+
+def full_input_set():
+    return np.concatenate([all_fp16_values(), special_values(), threshold_neighbours(), random_bits()])
