@@ -8,6 +8,7 @@
 
 #include "../../include/chatllm_hip.h"
 #include "glibc_math.h"
+#include "norm_order.h"
 #include "options.h"
 
 #define CLLM_WAVE 64
@@ -236,6 +237,111 @@ __device__ __forceinline__ double rms_block_sumsq_1024_one(f32x4 v, bool has, do
 #pragma unroll
     for (int w = 1; w < 16; w++) tot += part[w];
     return tot;
+}
+
+// ---- NORM: the workgroup's side of norm_order.h (the arithmetic, the serial chains and the two interval tests are stated there, once, for the device and for plain C).
+// A 1024-thread workgroup per row; thread t owns the groups of 8 elements t, t + 1024, ... -- the groups of ggml_vec_cvar_f32's AVX2 body, so that one thread forms a
+// whole h_g -- and, below n % 8, one leftover.  `first` = the caller's already-loaded group t (ignored when t >= n / 8); each part = 16 doubles of LDS.
+struct norm_g8 { f32x4 lo, hi; };
+__device__ __forceinline__ norm_g8 norm_load8(const float * x, int64_t g, bool aligned) { return norm_g8{ rms_load4(x, 2 * g, aligned), rms_load4(x, 2 * g + 1, aligned) }; }
+// S = sum x_i with A = sum |x_i| through the same tree (per-thread doubles, a DPP wave reduction, the 16 wave partials in wave order).  Contains a barrier.
+__device__ __forceinline__ void norm_block_sum_1024(const float * x, int64_t n, bool aligned, norm_g8 first, double * part_s, double * part_a, double & S, double & A) {
+    const int tid = threadIdx.x;
+    const int64_t ng = n >> 3;
+    double s = 0.0, a = 0.0;
+    norm_g8 v = first;
+    for (int64_t g = tid; g < ng; g += 1024) {
+        if (g != tid) v = norm_load8(x, g, aligned);
+        s += (double) v.lo.x; s += (double) v.lo.y; s += (double) v.lo.z; s += (double) v.lo.w; s += (double) v.hi.x; s += (double) v.hi.y; s += (double) v.hi.z; s += (double) v.hi.w;
+        a += (double) fabsf(v.lo.x); a += (double) fabsf(v.lo.y); a += (double) fabsf(v.lo.z); a += (double) fabsf(v.lo.w);
+        a += (double) fabsf(v.hi.x); a += (double) fabsf(v.hi.y); a += (double) fabsf(v.hi.z); a += (double) fabsf(v.hi.w);
+    }
+    if (8 * ng + tid < n) { const float t = x[8 * ng + tid]; s += (double) t; a += (double) fabsf(t); }
+    s = wave_sum_d(s); a = wave_sum_d(a);
+    if ((tid & 63) == 0) { part_s[tid >> 6] = s; part_a[tid >> 6] = a; }
+    __syncthreads();
+    S = part_s[0]; A = part_a[0];
+#pragma unroll
+    for (int w = 1; w < 16; w++) { S += part_s[w]; A += part_a[w]; }
+}
+// V = sum of the group sums h_g (each the reference's float tree, nm_group_h) and of the leftovers' squares, as a tree of doubles.  Contains a barrier.
+__device__ __forceinline__ double norm_block_var_sum_1024(const float * x, int64_t n, bool aligned, norm_g8 first, float mean, double * part) {
+    const int tid = threadIdx.x;
+    const int64_t ng = n >> 3;
+    double p = 0.0;
+    norm_g8 v = first;
+    for (int64_t g = tid; g < ng; g += 1024) {
+        if (g != tid) v = norm_load8(x, g, aligned);
+        p += (double) nm_group_h(v.lo.x - mean, v.lo.y - mean, v.lo.z - mean, v.lo.w - mean, v.hi.x - mean, v.hi.y - mean, v.hi.z - mean, v.hi.w - mean);
+    }
+    if (8 * ng + tid < n) { const float t = x[8 * ng + tid] - mean; p += (double)(t * t); }
+    p = wave_sum_d(p);
+    if ((tid & 63) == 0) part[tid >> 6] = p;
+    __syncthreads();
+    double V = part[0];
+#pragma unroll
+    for (int w = 1; w < 16; w++) V += part[w];
+    return V;
+}
+// the serial chains of norm_order.h (nm_serial_sum, nm_serial_var_sum: the same additions in the same order) by wave 0, off the straight-line code as rms_serial_sumsq
+// is and batched the same way: the 64 lanes fetch 64 consecutive terms at once (for V: lane l forms the h of group g0 + l), the chain then takes them lane by lane
+// through v_readlane, every lane computing the same total.  With one dependent load per term instead, a single row on this path cost a [512, 4096] launch 250 us.
+__device__ __forceinline__ double norm_chain(double acc, float term, int m) {          // acc += (double) term of lane 0, 1, ... m - 1, in that order
+    const int b = (int) __float_as_uint(term);
+    if (m == 64) {
+#pragma unroll 8
+        for (int k = 0; k < 64; k++) acc += (double) __uint_as_float((unsigned) __builtin_amdgcn_readlane(b, k));
+    } else {
+        for (int k = 0; k < m; k++) acc += (double) __uint_as_float((unsigned) __builtin_amdgcn_readlane(b, k));
+    }
+    return acc;
+}
+static __device__ __noinline__ double norm_serial_sum(const float * x, int64_t n) {
+    const int lane = threadIdx.x & 63;
+    double S = 0.0;
+    float cur = lane < n ? x[lane] : 0.0f;
+    for (int64_t i = 0; i < n; i += 64) {
+        const float nxt = i + 64 + lane < n ? x[i + 64 + lane] : 0.0f;      // the next batch is requested before this one is added
+        S = norm_chain(S, cur, n - i >= 64 ? 64 : (int)(n - i));
+        cur = nxt;
+    }
+    return S;
+}
+static __device__ __noinline__ double norm_serial_var_sum(const float * x, int64_t n, float mean) {
+    const int lane = threadIdx.x & 63;
+    const int64_t ng = n >> 3;
+    const bool aligned = (((uintptr_t) x) & 15) == 0;
+    double V = 0.0;
+    for (int64_t g0 = 0; g0 < ng; g0 += 64) {
+        float h = 0.0f;
+        if (g0 + lane < ng) {
+            const norm_g8 v = norm_load8(x, g0 + lane, aligned);
+            h = nm_group_h(v.lo.x - mean, v.lo.y - mean, v.lo.z - mean, v.lo.w - mean, v.hi.x - mean, v.hi.y - mean, v.hi.z - mean, v.hi.w - mean);
+        }
+        V = norm_chain(V, h, ng - g0 >= 64 ? 64 : (int)(ng - g0));
+    }
+    float q = 0.0f;
+    if (8 * ng + lane < n) { const float t = x[8 * ng + lane] - mean; q = t * t; }
+    return norm_chain(V, q, (int)(n & 7));
+}
+// mean and variance from the tree totals: where the interval test of norm_order.h cannot rule the order out, wave 0 redoes the sum in the reference's order.  The branches
+// are uniform over the workgroup (every thread holds the same totals).  x must still hold the row: no thread of an in-place launch stores before BOTH have returned,
+// and the barrier behind each serial pass is what keeps the others from doing so (as in rms_scale).  `slot`: one double of LDS each, distinct from the partials above.
+__device__ __forceinline__ float norm_mean(double S, double A, int64_t n, const float * x, double * slot) {
+    if (!nm_sum_order_safe(S, A, n)) {
+        if (threadIdx.x < 64) { const double s = norm_serial_sum(x, n); if (threadIdx.x == 0) *slot = s; }
+        __syncthreads();
+        S = *slot;
+    }
+    return nm_mean(S, n);
+}
+__device__ __forceinline__ float norm_variance(double V, int64_t n, float mean, const float * x, double * slot) {
+    if (!nm_var_order_safe(V, n)) {
+        if (threadIdx.x < 64) { const double s = norm_serial_var_sum(x, n, mean); if (threadIdx.x == 0) *slot = s; }
+        __syncthreads();
+        V = *slot;
+    }
+    return nm_variance(V, n);
 }
 
 // workgroup barrier for data exchanged through LDS only: __syncthreads() also drains vmcnt, i.e. waits for every global load in flight --

@@ -53,6 +53,55 @@ extern "C" int cllm_op_rms_norm_mul(void * stream, const cllm_tensor * src, cons
 }
 
 // ================================================================================================
+// NORM        ggml_compute_forward_norm_f32, ggml-cpu/ops.cpp:3643-3688 (LayerNorm before its affine: MUL and ADD stay nodes of their own)
+//   sum of x in double, mean -> float; the centred squares in float groups of 8, their sum in double, variance -> float;
+//   scale = 1/sqrtf(variance+eps), y = (x - mean) * scale.  The arithmetic and its order: norm_order.h; the workgroup's trees and fallbacks: common.h.
+// one workgroup per row, three passes over the row (the second and third hit the cache; a thread's first group of 8 stays in registers); float4 traffic where
+// the row start is 16-byte aligned.  dst may be src: every store comes after the last barrier of norm_variance, behind every read of the two sums.
+// ================================================================================================
+__global__ void __launch_bounds__(1024) k_norm(tview s, tview d, float eps) {
+    const int64_t row = blockIdx.x;
+    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
+    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
+    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const int64_t n = s.ne[0], ng = n >> 3;
+    const int tid = threadIdx.x;
+    __shared__ double part[3][16];
+    __shared__ double slot[2];
+    const bool aligned = (((uintptr_t) x) & 15) == 0, y_aligned = (((uintptr_t) y) & 15) == 0;
+    const norm_g8 first = tid < ng ? norm_load8(x, tid, aligned) : norm_g8{ f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0} };
+    double S, A;
+    norm_block_sum_1024(x, n, aligned, first, part[0], part[1], S, A);
+    const float mean = norm_mean(S, A, n, x, &slot[0]);
+    const double V = norm_block_var_sum_1024(x, n, aligned, first, mean, part[2]);
+    const float scale = nm_scale(norm_variance(V, n, mean, x, &slot[1]), eps);
+    norm_g8 v = first;
+    for (int64_t g = tid; g < ng; g += 1024) {
+        if (g != tid) v = norm_load8(x, g, aligned);
+        const f32x4 lo = { nm_out(v.lo.x, mean, scale), nm_out(v.lo.y, mean, scale), nm_out(v.lo.z, mean, scale), nm_out(v.lo.w, mean, scale) };
+        const f32x4 hi = { nm_out(v.hi.x, mean, scale), nm_out(v.hi.y, mean, scale), nm_out(v.hi.z, mean, scale), nm_out(v.hi.w, mean, scale) };
+        float * yg = y + 8 * g;
+        if (y_aligned) { *(f32x4 *) yg = lo; *(f32x4 *)(yg + 4) = hi; }
+        else { yg[0] = lo.x; yg[1] = lo.y; yg[2] = lo.z; yg[3] = lo.w; yg[4] = hi.x; yg[5] = hi.y; yg[6] = hi.z; yg[7] = hi.w; }
+    }
+    if (8 * ng + tid < n) y[8 * ng + tid] = nm_out(x[8 * ng + tid], mean, scale);
+}
+
+extern "C" int cllm_op_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "norm: null");
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "norm: type (F32 only)");
+    if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "norm: shape");
+    if (!(eps >= 0.0f)) FAIL(CLLM_E_INVALID, "norm: eps must be >= 0");             // (NaN included) the reference asserts eps >= 0, ops.cpp:3661
+    if (src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "norm: rows must be dense");
+    const int64_t rows = t_nrows(src);
+    if (rows == 0 || src->ne[0] == 0) return CLLM_OK;
+    if (rows > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "norm: more than 2^31 - 1 rows");
+    hipLaunchKernelGGL(k_norm, dim3((unsigned) rows), dim3(1024), 0, (hipStream_t) stream, tv(src), tv(dst), eps);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// ================================================================================================
 // ROPE        ggml_compute_forward_rope_flt<float>, ggml-cpu/ops.cpp:5589-5865
 //   theta_i built by ITERATED fp32 multiplication (theta *= theta_scale), cos/sin per (token, pair),
 //   YaRN mixing (rope_yarn :5596-5611).  One workgroup per token: the first n_dims/2 threads build

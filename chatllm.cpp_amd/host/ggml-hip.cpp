@@ -393,6 +393,10 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
                    (b->ne[1] == 1 || b->ne[1] == op->src[2]->ne[0]) && op->src[2]->ne[0] * op->src[2]->ne[1] <= 65535 && b->nb[1] % 16 == 0 && b->nb[2] % 16 == 0 &&
                    (a->type != GGML_TYPE_Q4_K || (a->nb[1] % 16 == 0 && a->nb[2] % 16 == 0)) && (a->type != GGML_TYPE_Q4_1 || (a->nb[1] % 4 == 0 && a->nb[2] % 4 == 0));
         case GGML_OP_RMS_NORM: return f32_dense(a) && op->type == GGML_TYPE_F32;
+        case GGML_OP_NORM: {       // cllm_op_norm's own predicates: dense F32 rows on both sides, eps >= 0 (not NaN); MUL and ADD of a LayerNorm's affine stay their own nodes
+            float eps; memcpy(&eps, op->op_params, 4);
+            return f32_dense(a) && op->type == GGML_TYPE_F32 && op->nb[0] == 4 && eps >= 0.0f;
+        }
         case GGML_OP_ADD: case GGML_OP_MUL: case GGML_OP_DIV: return a->type == GGML_TYPE_F32 && b->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && ggml_can_repeat(b, a);
         case GGML_OP_SUM_ROWS: return f32_dense(a) && f32_dense(op);
         case GGML_OP_TOP_K: return f32_dense(a) && op->type == GGML_TYPE_I32 && a->ne[0] <= 4096;
@@ -979,6 +983,7 @@ ggml_status walk(walk_ctx & w, fuse_plan & plan, sig_writer * sw) {
             case GGML_OP_MUL_MAT:        rc = alt == ALT_FLASH_PREFILL ? issue_flash_prefill(w, plan, i, io) : plan.mv[i] >= 0 ? issue_fused_mat_vec(w, plan, i, io) : plan.pf[i] >= 0 ? issue_prefill_mat_mul(w, plan, i, io) : issue_mat_mul(w, io); break;
             case GGML_OP_MUL_MAT_ID:     rc = issue_mat_mul_id(w, io); break;
             case GGML_OP_RMS_NORM:       { float eps; memcpy(&eps, n->op_params, 4); rc = E(cllm_op_rms_norm, st, &da, &d, eps); } break;
+            case GGML_OP_NORM:           { float eps; memcpy(&eps, n->op_params, 4); rc = E(cllm_op_norm, st, &da, &d, eps); } break;
             case GGML_OP_ADD:            rc = alt == ALT_MOE_COMBINE ? issue_moe_combine(w, plan, i, io) : E(cllm_op_add, st, &da, &db, &d); break;
             case GGML_OP_MUL:            rc = issue_mul(w, plan, i, io); break;
             case GGML_OP_DIV:            rc = E(cllm_op_div, st, &da, &db, &d); break;

@@ -75,6 +75,13 @@ def rms_norm_mul(a, weight, eps, dst=None):
     return dst
 
 
+def norm(a, eps, dst=None):
+    """ggml::norm / norm_inplace (dst is a): LayerNorm before its affine, which stays mul(weight) and add(bias)"""
+    dst = dst or Tensor(F32, a.ne)
+    _l.check(_l.get().cllm_op_norm(None, _ref(a), _ref(dst), eps), "norm")
+    return dst
+
+
 def rope_ext(a, pos, freq_factors, n_dims, mode, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0,
              attn_factor=1.0, beta_fast=0.0, beta_slow=0.0, inplace=False):
     """ggml::rope_ext / rope_ext_inplace"""

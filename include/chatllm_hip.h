@@ -215,6 +215,12 @@ CLLM_API int    cllm_vec_dot_isums(void * stream, int wtype, int64_t k, const vo
 CLLM_API int cllm_op_rms_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps);
 /* fused RMS_NORM + MUL(weight) -- chatllm RMSNorm::forward (src/layers.cpp:2216-2225); same two roundings */
 CLLM_API int cllm_op_rms_norm_mul(void * stream, const cllm_tensor * src, const cllm_tensor * weight, cllm_tensor * dst, float eps);
+/* GGML_OP_NORM          ggml_compute_forward_norm_f32  (ggml-cpu/ops.cpp:3643-3688; ggml_vec_sum_f32 vec.h:1510-1520, ggml_vec_cvar_f32 vec.cpp:471-545, its AVX2 branch):
+ * what the host builds every LayerNorm from (ggml::norm / norm_inplace, then MUL(weight) and ADD(bias) as nodes of their own: src/layers.cpp:854-877, 2153-2204).
+ * F32 -> F32, rows of any ne[0] >= 1 with nb[0] == 4 (nb[1..3] free), dst may be src; every word has the bits of the reference's x86-64-v3 CPU build (a row holding
+ * a NaN or an inf is NaN in every element, as there; NaN payloads are not part of the contract).  CLLM_E_UNSUPPORTED: another type, rows that are not dense;
+ * CLLM_E_INVALID: null, shapes that differ, eps < 0 or NaN (the reference asserts eps >= 0).  An empty tensor: CLLM_OK, no launch.  A declined call leaves dst untouched. */
+CLLM_API int cllm_op_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps);
 
 typedef struct cllm_rope_params {      /* op_params of GGML_OP_ROPE (ggml.c ggml_rope_impl) */
     int32_t n_dims, mode, n_ctx_orig;  /* mode 0 = NORMAL (i,i+1), 2 = NEOX (i, i+n_dims/2) */
