@@ -500,7 +500,9 @@ __global__ void __launch_bounds__(256) k_elementwise(tview a, tview b, tview d, 
         const float x = *(const float *)(a.data + i0*a.nb[0] + i1*a.nb[1] + i2*a.nb[2] + i3*a.nb[3]);
         float y;
         if (OP == EW_DIAG_MASK)      y = (i0 > (int64_t) i0p + i1) ? -INFINITY : x;      // ops.cpp:5137-5185
-        else if (OP == EW_SCALE)     y = (f1 == 0.0f) ? x * f0 : x * f0 + f1;            // ggml_vec_scale_f32 / ggml_vec_mad1_f32
+        // ggml_vec_scale_f32 / ggml_vec_mad1_f32 (vec.h:667-712): with a bias the reference build rounds once in every element of a row, the
+        // _mm256_fmadd_ps body and the leftovers alike (gcc contracts their x[i]*s + b): tests/test_elementwise_model.py
+        else if (OP == EW_SCALE)     y = (f1 == 0.0f) ? x * f0 : __builtin_fmaf(x, f0, f1);
         else if (OP == EW_SILU) {
             // ggml_vec_silu_f32 (vec.cpp:396-431): AVX2 body for i0 < (ne0 & ~7), scalar expf tail
             y = (i0 < (d.ne[0] & ~(int64_t) 7)) ? x / (1.0f + ggml_expf_poly(0.0f - x)) : x / (1.0f + libm_expf(-x));

@@ -234,7 +234,7 @@ CLLM_API int cllm_op_soft_max(void * stream, const cllm_tensor * src, const cllm
                               float scale, float max_bias);
 /* GGML_OP_DIAG_MASK_INF ggml_compute_forward_diag_mask_f32 (ops.cpp:5137-5185) */
 CLLM_API int cllm_op_diag_mask_inf(void * stream, const cllm_tensor * src, cllm_tensor * dst, int n_past);
-/* GGML_OP_SCALE         ggml_compute_forward_scale (ops.cpp:4426-) y = x*s + b */
+/* GGML_OP_SCALE         ggml_compute_forward_scale (ops.cpp:4426-) y = x*s when b == 0, else fma(x, s, b): one rounding, as the reference build's ggml_vec_mad1_f32 */
 CLLM_API int cllm_op_scale(void * stream, const cllm_tensor * src, cllm_tensor * dst, float s, float b);
 /* fused SCALE + DIAG_MASK_INF + SOFT_MAX as chatllm's attn_scores_to_probs emits them (src/layers.cpp:2499-2539) */
 CLLM_API int cllm_op_scale_mask_soft_max(void * stream, const cllm_tensor * src, cllm_tensor * dst, float scale, int n_past);

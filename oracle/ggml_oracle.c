@@ -1597,8 +1597,11 @@ int orc_scale(const orc_tensor * src, orc_tensor * dst, float s, float b) {
     for (int64_t i3 = 0; i3 < src->ne[3]; i3++) for (int64_t i2 = 0; i2 < src->ne[2]; i2++)
     for (int64_t i1 = 0; i1 < src->ne[1]; i1++) for (int64_t i0 = 0; i0 < src->ne[0]; i0++) {
         const float v = *(const float *) tptr(src, i0, i1, i2, i3);
-        /* ggml_vec_scale_f32 when b == 0, ggml_vec_mad1_f32 otherwise */
-        *(float *) tptr(dst, i0, i1, i2, i3) = (b == 0.0f) ? v * s : v * s + b;
+        /* ggml_vec_scale_f32 when b == 0, ggml_vec_mad1_f32 (vec.h:667-712) otherwise.  In the reference's x86-64-v3 build the latter rounds ONCE in
+         * every element of a row: the body i0 < (ne0 & ~31) is _mm256_fmadd_ps, and gcc contracts the leftovers' `x[i]*s + b` into an fma too
+         * (its -ffp-contract=fast default), so the tail i0 >= (ne0 & ~31) is single-rounded as well.  Found by comparing ggml_scale_bias of
+         * libggml-cpu.so with both forms at row lengths 1 .. 4097, word for word: tests/test_elementwise_model.py */
+        *(float *) tptr(dst, i0, i1, i2, i3) = (b == 0.0f) ? v * s : fmaf(v, s, b);
     }
     return 0;
 }

@@ -1,7 +1,8 @@
 """The reference's own CPU backend (oracle/_ref/libggml-cpu.so over libggml-base.so, built from the reference by oracle/Makefile) driven
 through its public ggml C API with ctypes: ggml_init, ggml_new_tensor_4d, the op constructor, ggml_build_forward_expand,
 ggml_graph_compute_with_ctx.  The oracle of the element-wise ops that oracle/ref_ops.c does not expose (TANH, RELU, SIGMOID, GELU,
-GELU_QUICK, SQR).  Also: the input sets the CPU and the GPU tests of these ops share."""
+GELU_QUICK, SQR), of SCALE with a bias, broadcast ADD / MUL / DIV, DIAG_MASK_INF and of ROPE over a view (ggml_view_4d), out of place and
+in place.  Also: the input sets the CPU and the GPU tests of the unary ops share."""
 import ctypes as C
 import os
 
@@ -13,6 +14,8 @@ GGML_TYPE_F32 = 0
 TANH, RELU, SIGMOID, GELU, GELU_QUICK, SQR = 4, 6, 7, 8, 9, -1
 OPS = {"tanh": TANH, "relu": RELU, "sigmoid": SIGMOID, "gelu": GELU, "gelu_quick": GELU_QUICK, "sqr": SQR}
 _CTOR = {TANH: "ggml_tanh", RELU: "ggml_relu", SIGMOID: "ggml_sigmoid", GELU: "ggml_gelu", GELU_QUICK: "ggml_gelu_quick", SQR: "ggml_sqr"}
+_BINARY = {"add": "ggml_add", "mul": "ggml_mul", "div": "ggml_div"}
+GGML_TYPE_I32 = 26
 
 
 class _InitParams(C.Structure):
@@ -44,6 +47,13 @@ def libs():
         base.ggml_tensor_overhead.restype, base.ggml_graph_overhead.restype = C.c_size_t, C.c_size_t
         for name in _CTOR.values():
             getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P]
+        for name in _BINARY.values():
+            getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P]
+        base.ggml_scale_bias.restype, base.ggml_scale_bias.argtypes = P, [P, P, C.c_float, C.c_float]
+        base.ggml_diag_mask_inf.restype, base.ggml_diag_mask_inf.argtypes = P, [P, P, C.c_int]
+        base.ggml_view_4d.restype, base.ggml_view_4d.argtypes = P, [P, P] + [C.c_int64] * 4 + [C.c_size_t] * 4
+        for name in ("ggml_rope_ext", "ggml_rope_ext_inplace"):
+            getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P, P, C.c_int, C.c_int, C.c_int] + [C.c_float] * 6
         cpu.ggml_cpu_init.restype, cpu.ggml_cpu_init.argtypes = None, []
         cpu.ggml_graph_compute_with_ctx.restype, cpu.ggml_graph_compute_with_ctx.argtypes = C.c_int, [P, P, C.c_int]
         base.ggml_fp32_to_fp16_row.restype, base.ggml_fp32_to_fp16_row.argtypes = None, [P, P, C.c_int64]
@@ -73,6 +83,106 @@ def unary(op, x):
         return out
     finally:
         base.ggml_free(ctx)
+
+
+def _ne(x):
+    """ne[4] of a numpy array of up to 4 dimensions (numpy order = reversed ne)"""
+    return list(reversed(x.shape)) + [1] * (4 - x.ndim)
+
+
+def _new(base, ctx, x, type_=GGML_TYPE_F32):
+    """a dense tensor of the context holding x"""
+    t = base.ggml_new_tensor_4d(ctx, type_, *_ne(x))
+    C.memmove(base.ggml_get_data(t), x.ctypes.data, x.nbytes)
+    return t
+
+
+def _graph(nbytes, build):
+    """one context, one graph of the node build(base, ctx) returns, one thread; build's second result says what to read back (a list of
+    (tensor, shape, dtype)); returns those arrays"""
+    base, cpu = libs()
+    mem = nbytes + 16 * base.ggml_tensor_overhead() + base.ggml_graph_overhead() + (1 << 16)
+    ctx = base.ggml_init(_InitParams(mem, None, False))
+    assert ctx
+    try:
+        d, reads = build(base, ctx)
+        g = base.ggml_new_graph(ctx)
+        base.ggml_build_forward_expand(g, d)
+        assert cpu.ggml_graph_compute_with_ctx(ctx, g, 1) == 0
+        outs = []
+        for t, shape, dtype in reads:
+            out = np.empty(shape, dtype)
+            C.memmove(out.ctypes.data, base.ggml_get_data(t), out.nbytes)
+            outs.append(out)
+        return outs
+    finally:
+        base.ggml_free(ctx)
+
+
+def scale_bias(x, s, b):
+    """ggml_scale_bias(x, s, b): x * s + b as the reference's SCALE node computes it (ggml_vec_scale_f32 when b == 0, ggml_vec_mad1_f32 per row
+    otherwise), same shape"""
+    x = np.ascontiguousarray(x, np.float32)
+
+    def build(base, ctx):
+        d = base.ggml_scale_bias(ctx, _new(base, ctx, x), C.c_float(s), C.c_float(b))
+        return d, [(d, x.shape, np.float32)]
+    return _graph(2 * x.nbytes, build)[0]
+
+
+def binary(op, a, b):
+    """ggml_add / ggml_mul / ggml_div (op: "add", "mul", "div") of a and a b that repeats into a (ggml_can_repeat: every ne of a is a multiple
+    of b's); both dense; the shape of a"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+
+    def build(base, ctx):
+        d = getattr(base, _BINARY[op])(ctx, _new(base, ctx, a), _new(base, ctx, b))
+        return d, [(d, a.shape, np.float32)]
+    return _graph(2 * a.nbytes + b.nbytes, build)[0]
+
+
+def diag_mask_inf(x, n_past):
+    """ggml_diag_mask_inf(x, n_past): -inf where i0 > n_past + i1"""
+    x = np.ascontiguousarray(x, np.float32)
+
+    def build(base, ctx):
+        d = base.ggml_diag_mask_inf(ctx, _new(base, ctx, x), n_past)
+        return d, [(d, x.shape, np.float32)]
+    return _graph(2 * x.nbytes, build)[0]
+
+
+ROPE_DEFAULTS = dict(n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0, attn_factor=1.0, beta_fast=0.0, beta_slow=0.0)
+
+
+def rope(parent, view_ne, view_nb, view_offset, pos, ff, params, inplace):
+    """ggml_rope_ext (or ggml_rope_ext_inplace) over ggml_view_4d(parent, view_ne, view_nb[1..3], view_offset) of a dense float32 parent.
+    pos: int32 [view_ne[2]]; ff: the frequency factors, float32 [>= n_dims / 2], or None; params: n_dims, mode and any of ROPE_DEFAULTS.
+    Returns (the result as a dense array of shape reversed(view_ne), the parent's buffer after the run); in place the result is the view's
+    content read out of that buffer"""
+    parent = np.ascontiguousarray(parent, np.float32)
+    pos = np.ascontiguousarray(pos, np.int32)
+    ff = None if ff is None else np.ascontiguousarray(ff, np.float32)
+    ne = [int(v) for v in view_ne] + [1] * (4 - len(view_ne))
+    nb = [int(v) for v in view_nb]
+    p = dict(ROPE_DEFAULTS, **params)
+    shape = tuple(reversed(ne))
+
+    def build(base, ctx):
+        par = _new(base, ctx, parent)
+        v = base.ggml_view_4d(ctx, par, ne[0], ne[1], ne[2], ne[3], nb[1], nb[2], nb[3], view_offset)
+        tp = _new(base, ctx, pos, GGML_TYPE_I32)
+        tf = _new(base, ctx, ff) if ff is not None else None
+        ctor = base.ggml_rope_ext_inplace if inplace else base.ggml_rope_ext
+        d = ctor(ctx, v, tp, tf, p["n_dims"], p["mode"], p["n_ctx_orig"], p["freq_base"], p["freq_scale"], p["ext_factor"], p["attn_factor"],
+                 p["beta_fast"], p["beta_slow"])
+        return d, [(par, parent.shape, np.float32)] + ([] if inplace else [(d, shape, np.float32)])
+    outs = _graph(2 * parent.nbytes + pos.nbytes + (ff.nbytes if ff is not None else 0) + 4 * (ne[0] + 64), build)
+    after = outs[0]
+    if inplace:
+        result = np.lib.stride_tricks.as_strided(after.reshape(-1)[view_offset // 4:], shape, (nb[3], nb[2], nb[1], nb[0])).copy()
+    else:
+        result = outs[1]
+    return result, after
 
 
 def gelu_tables():

@@ -49,3 +49,21 @@ def test_oracle_llama_is_causal_and_deterministic(pkg):
         lb = b.forward([t])
     assert np.allclose(la, lb, rtol=0, atol=2e-4)
     assert np.isfinite(la).all() and la.std() > 0.05
+
+
+def test_the_fusion_planner_declines_a_scale_with_a_bias():
+    """SCALE -> DIAG_MASK_INF -> SOFT_MAX becomes cllm_op_scale_mask_soft_max, which has no bias: the planner (host/fuse_plan.h) may take the chain
+    only when the SCALE node's op_params[1] is 0, and both fused attention forms start from a chain it took (sm_src).  The module has no graph-level
+    harness on the CPU, so this reads the planner's text: the condition that sets sm_src names the bias, and plan_attention skips every SOFT_MAX
+    without an sm_src before it reads the SCALE node's factor"""
+    import os
+    import re
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(here, "chatllm.cpp_amd", "host", "fuse_plan.h")).read()
+    takes = [line for line in text.splitlines() if re.search(r"P\.sm_src\[i\]\s*=\s*sc\b", line)]
+    assert len(takes) == 1, takes
+    cond = takes[0][:takes[0].index("P.sm_src[i]")]
+    assert "bias == 0.0f" in cond and re.search(r"memcpy\(&bias, \(const float \*\) ggml_graph_node\(g, sc\)->op_params \+ 1, 4\)", text)
+    attention = text[text.index("void plan_attention("):text.index("fuse_plan make_plan(")]
+    assert attention.index("if (P.sm_src[i] < 0) continue;") < attention.index("scn->op_params")
+    assert len(re.findall(r"scn = node\(P\.sm_src\[i\]\)", attention)) == 1 and "GGML_OP_SCALE" not in attention
