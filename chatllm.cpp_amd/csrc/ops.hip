@@ -692,7 +692,7 @@ __global__ void __launch_bounds__(256) k_set_rows_q8_0(tview s, tview idx, tview
         const int64_t row = (int64_t) *(const IDX *)(idx.data + i*idx.nb[0] + (i2 % idx.ne[1])*idx.nb[1] + (i3 % idx.ne[2])*idx.nb[2]);
         const f32x4 v = *(const f32x4 *)(s.data + (blk * 32 + sub * 4) * 4 + i*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
         float dd; int ss;
-        const uint32_t p = quant4_q8_0<false>(v, &dd, &ss);
+        const uint32_t p = quant4_q8_0<false, true>(v, &dd, &ss);      // SAT: an inverse scale that overflows gives 32 quants of -128, as the CPU's saturating packs do
         if (!live || row < 0 || row >= d.ne[1]) continue;
         char * dp = d.data + row*d.nb[1] + i2*d.nb[2] + i3*d.nb[3] + blk * 34;
         if (sub == 0) *(uint16_t *) dp = f2h(dd);

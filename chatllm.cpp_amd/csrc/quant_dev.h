@@ -12,13 +12,16 @@ __device__ __forceinline__ uint32_t pack4(int q0, int q1, int q2, int q3) {
 // 8 consecutive lanes hold one 32-block (4 values each).  Returns the packed int8 quads; *d (fp16-rounded scale as
 // f32) and *s (sum of the block's int8) are valid on every lane of the 8-lane group.
 // Q81 (quantize_row_q8_1, arch/x86/quants.c:388-480): the same quants; *s = the bits of fp16(d * sum) as f32, d NOT yet rounded.
-template <bool Q81 = false>
+// SAT (the KV-cache write, whose bytes are compared with the reference's): where 127 / amax overflows to inf (0 < amax < 3.74e-37) the CPU's products are +-inf or,
+// for the block's zeros, NaN; _mm256_cvtps_epi32 makes 0x80000000 of both and the saturating packs -128: all 32 quants are 0x80 (the stored scale is fp16 0)
+template <bool Q81 = false, bool SAT = false>
 __device__ __forceinline__ uint32_t quant4_q8_0(f32x4 v, float * d_out, int * s_out) {
     float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     amax = group8_max(amax);
     const float d  = amax / 127.f;
     const float id = (amax != 0.0f) ? 127.f / amax : 0.0f;
-    const int q0 = (int) rintf(v.x * id), q1 = (int) rintf(v.y * id), q2 = (int) rintf(v.z * id), q3 = (int) rintf(v.w * id);
+    int q0 = (int) rintf(v.x * id), q1 = (int) rintf(v.y * id), q2 = (int) rintf(v.z * id), q3 = (int) rintf(v.w * id);
+    if (SAT && id == INFINITY) q0 = q1 = q2 = q3 = -128;
     const int s = group8_sum_i(q0 + q1 + q2 + q3);
     *d_out = h2f(f2h(d));              // the CPU stores d as fp16 and reads it back for the dot product
     *s_out = Q81 ? __float_as_int(h2f(f2h(d * (float) s))) : s;

@@ -97,7 +97,15 @@ uint16_t orc_fp32_to_fp16(float f) {
 /* ------------------------------------------------------------------------------------------ */
 /* activation quantizers                                                                       */
 /* ------------------------------------------------------------------------------------------ */
-/* arch/x86/quants.c:290-386 (AVX2): d = amax/127 stored as fp16; q = cvt(round_nearest_even(x * (127/amax))) */
+/* _mm256_cvtps_epi32 of the rounded product, then _mm256_packs_epi32 and _mm256_packs_epi16 (both saturating): NaN and everything outside int32 become
+ * 0x80000000, which saturates to -128.  Reached where 127/amax overflows to inf (0 < amax < 3.74e-37, every subnormal): x*id is +-inf, or NaN for the block's zeros */
+static inline int8_t cvt_packs_i8(float v) {
+    if (v != v || fabsf(v) >= 0x1p31f) return -128;
+    const int q = (int) nearbyintf(v);              /* nearbyintf under the default rounding mode == _mm256_round_ps(NEAREST) == half-to-even */
+    return (int8_t)(q < -128 ? -128 : q > 127 ? 127 : q);
+}
+
+/* arch/x86/quants.c:290-386 (AVX2): d = amax/127 stored as fp16; q = packs(cvt(round_nearest_even(x * (127/amax)))) */
 void orc_quantize_row_q8_0(const float * x, orc_block_q8_0 * y, int64_t k) {
     const int64_t nb = k / ORC_QK;
     for (int64_t i = 0; i < nb; i++) {
@@ -106,10 +114,7 @@ void orc_quantize_row_q8_0(const float * x, orc_block_q8_0 * y, int64_t k) {
         const float d  = amax / 127.f;
         const float id = (amax != 0.0f) ? 127.f / amax : 0.0f;
         y[i].d = orc_fp32_to_fp16(d);
-        for (int j = 0; j < ORC_QK; j++) {
-            /* nearbyintf under the default rounding mode == _mm256_round_ps(NEAREST) == half-to-even */
-            y[i].qs[j] = (int8_t)(int) nearbyintf(x[i*ORC_QK + j] * id);
-        }
+        for (int j = 0; j < ORC_QK; j++) y[i].qs[j] = cvt_packs_i8(x[i*ORC_QK + j] * id);
     }
 }
 
@@ -1670,9 +1675,10 @@ int orc_top_k(const orc_tensor * src, orc_tensor * dst) {
 /* KV-cache writes and gathers                                                                 */
 /* ------------------------------------------------------------------------------------------ */
 int orc_set_rows(const orc_tensor * src, const orc_tensor * idx, orc_tensor * dst) {
-    if (src->type != ORC_F32 || (dst->type != ORC_F16 && dst->type != ORC_F32)) return -1;
+    if (src->type != ORC_F32 || (dst->type != ORC_F16 && dst->type != ORC_F32 && dst->type != ORC_Q8_0)) return -1;
     if (idx->type != ORC_I32 && idx->type != ORC_I64) return -2;
     if (dst->ne[0] != src->ne[0] || dst->ne[2] != src->ne[2] || dst->ne[3] != src->ne[3]) return -3;
+    if (dst->type == ORC_Q8_0 && src->ne[0] % ORC_QK) return -3;
     if (idx->ne[0] != src->ne[1] || src->ne[2] % idx->ne[1] || src->ne[3] % idx->ne[2]) return -4;
     for (int64_t i3 = 0; i3 < src->ne[3]; i3++) for (int64_t i2 = 0; i2 < src->ne[2]; i2++)
     for (int64_t i = 0; i < src->ne[1]; i++) {
@@ -1681,6 +1687,8 @@ int orc_set_rows(const orc_tensor * src, const orc_tensor * idx, orc_tensor * ds
         if (r < 0 || r >= dst->ne[1]) return -5;
         const float * x = (const float *) tptr(src, 0, i, i2, i3);
         char * y = tptr(dst, 0, r, i2, i3);
+        /* from_float of the CPU traits: quantize_row_q8_0 (the x86 branch), not quantize_row_q8_0_ref */
+        if (dst->type == ORC_Q8_0) { orc_quantize_row_q8_0(x, (orc_block_q8_0 *) y, src->ne[0]); continue; }
         for (int64_t c = 0; c < src->ne[0]; c++) {
             if (dst->type == ORC_F16) ((uint16_t *) y)[c] = orc_fp32_to_fp16(x[c]);
             else                      ((float    *) y)[c] = x[c];
@@ -1693,7 +1701,19 @@ int orc_set_rows(const orc_tensor * src, const orc_tensor * idx, orc_tensor * ds
 int orc_cpy(const orc_tensor * src, orc_tensor * dst) {
     const int64_t n = src->ne[0]*src->ne[1]*src->ne[2]*src->ne[3];
     if (n != dst->ne[0]*dst->ne[1]*dst->ne[2]*dst->ne[3]) return -1;
-    if ((src->type != ORC_F32 && src->type != ORC_F16) || (dst->type != ORC_F32 && dst->type != ORC_F16)) return -2;
+    if (src->type == dst->type && orc_blck_size(src->type) > 1) {
+        /* the same quantized type on both sides (ggml_compute_forward_dup_bytes): whole rows move; row e of src, row-major over ne[1..3], to row e of dst */
+        if (src->ne[0] != dst->ne[0] || src->nb[0] != orc_type_size(src->type) || dst->nb[0] != src->nb[0]) return -3;
+        const size_t rs = orc_row_size(src->type, src->ne[0]);
+        for (int64_t e = 0; e < nrows(src); e++) {
+            const int64_t s1 = e % src->ne[1], s2 = (e / src->ne[1]) % src->ne[2], s3 = e / (src->ne[1]*src->ne[2]);
+            const int64_t d1 = e % dst->ne[1], d2 = (e / dst->ne[1]) % dst->ne[2], d3 = e / (dst->ne[1]*dst->ne[2]);
+            memcpy(tptr(dst, 0, d1, d2, d3), tptr(src, 0, s1, s2, s3), rs);
+        }
+        return 0;
+    }
+    if (src->type == ORC_I32 || dst->type == ORC_I32) { if (src->type != dst->type) return -2; }      /* I32 only to I32: bytes */
+    else if ((src->type != ORC_F32 && src->type != ORC_F16) || (dst->type != ORC_F32 && dst->type != ORC_F16)) return -2;
     for (int64_t e = 0; e < n; e++) {
         int64_t r = e;
         const int64_t s0 = r % src->ne[0]; r /= src->ne[0];

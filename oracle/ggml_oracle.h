@@ -77,7 +77,7 @@ float    orc_fp16_to_fp32(uint16_t h);
 uint16_t orc_fp32_to_fp16(float f);
 
 /* ---- activation quantizers ---- */
-/* x86 AVX2 branch: id = 127/amax, round-half-even   (ggml-cpu/arch/x86/quants.c:290-386) */
+/* x86 AVX2 branch: id = 127/amax, round-half-even, saturating packs (all -128 where id overflows)   (ggml-cpu/arch/x86/quants.c:290-386) */
 void orc_quantize_row_q8_0(const float * x, orc_block_q8_0 * y, int64_t k);
 /* portable branch: id = 1/d, roundf (half away)      (ggml/src/ggml-quants.c:199-222)      */
 void orc_quantize_row_q8_0_ref(const float * x, orc_block_q8_0 * y, int64_t k);
@@ -207,9 +207,9 @@ int orc_div(const orc_tensor * a, const orc_tensor * b, orc_tensor * dst);     /
 /* the router of a sparse-MoE block (GenericSparseMLP::forward, src/layers.cpp:3755-3815) */
 int orc_sum_rows(const orc_tensor * src, orc_tensor * dst);                     /* ops.cpp:1451-1482, double accumulator (vec.h:1510-1520) */
 int orc_top_k(const orc_tensor * src, orc_tensor * dst);                        /* ops.cpp:8057-8094: descending, first two swapped */
-/* ggml_compute_forward_set_rows_f32 (ops.cpp:4892-4940): dst rows (F16|F32) <- src rows (F32) at idx (I32|I64) */
+/* ggml_compute_forward_set_rows_f32 (ops.cpp:4892-4940): dst rows (F16|F32|Q8_0, the last through orc_quantize_row_q8_0) <- src rows (F32) at idx (I32|I64) */
 int orc_set_rows(const orc_tensor * src, const orc_tensor * idx, orc_tensor * dst);
-/* ggml_compute_forward_dup / cpy (ops.cpp:47-330,526): same #elements, F32->F32|F16, F16->F16|F32, any strides */
+/* ggml_compute_forward_dup / cpy (ops.cpp:47-330,526): same #elements, F32->F32|F16, F16->F16|F32, I32->I32, any strides; a quantized type to itself: whole rows */
 int orc_cpy(const orc_tensor * src, orc_tensor * dst);
 /* ggml_compute_forward_get_rows (ops.cpp:4653-4700,4820): dst F32 rows <- dequant(src rows[idx]) */
 int orc_get_rows(const orc_tensor * src, const orc_tensor * idx, orc_tensor * dst);

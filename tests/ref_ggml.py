@@ -2,7 +2,8 @@
 through its public ggml C API with ctypes: ggml_init, ggml_new_tensor_4d, the op constructor, ggml_build_forward_expand,
 ggml_graph_compute_with_ctx.  The oracle of the element-wise ops that oracle/ref_ops.c does not expose (TANH, RELU, SIGMOID, GELU,
 GELU_QUICK, SQR), of SCALE with a bias, broadcast ADD / MUL / DIV, DIAG_MASK_INF and of ROPE over a view (ggml_view_4d), out of place and
-in place.  Also: the input sets the CPU and the GPU tests of the unary ops share."""
+in place; of SET_ROWS, CPY / CONT, GET_ROWS between views (ggml_view_4d, ggml_permute, ggml_transpose) and of SOFT_MAX with a mask tensor.
+Also: the input sets the CPU and the GPU tests of the unary ops share."""
 import ctypes as C
 import os
 
@@ -16,6 +17,9 @@ OPS = {"tanh": TANH, "relu": RELU, "sigmoid": SIGMOID, "gelu": GELU, "gelu_quick
 _CTOR = {TANH: "ggml_tanh", RELU: "ggml_relu", SIGMOID: "ggml_sigmoid", GELU: "ggml_gelu", GELU_QUICK: "ggml_gelu_quick", SQR: "ggml_sqr"}
 _BINARY = {"add": "ggml_add", "mul": "ggml_mul", "div": "ggml_div"}
 GGML_TYPE_I32 = 26
+GGML_TYPE_F16, GGML_TYPE_Q8_0, GGML_TYPE_I64 = 1, 8, 27
+# (bytes of a block, elements of a block) of the types the data-movement entry points take: ggml.c type_traits
+_BLOCK = {0: (4, 1), 1: (2, 1), 26: (4, 1), 27: (8, 1), 2: (18, 32), 8: (34, 32), 12: (144, 256), 14: (210, 256)}
 
 
 class _InitParams(C.Structure):
@@ -52,6 +56,16 @@ def libs():
         base.ggml_scale_bias.restype, base.ggml_scale_bias.argtypes = P, [P, P, C.c_float, C.c_float]
         base.ggml_diag_mask_inf.restype, base.ggml_diag_mask_inf.argtypes = P, [P, P, C.c_int]
         base.ggml_view_4d.restype, base.ggml_view_4d.argtypes = P, [P, P] + [C.c_int64] * 4 + [C.c_size_t] * 4
+        base.ggml_permute.restype, base.ggml_permute.argtypes = P, [P, P] + [C.c_int] * 4
+        base.ggml_transpose.restype, base.ggml_transpose.argtypes = P, [P, P]
+        base.ggml_new_tensor_1d.restype, base.ggml_new_tensor_1d.argtypes = P, [P, C.c_int, C.c_int64]
+        for name in ("ggml_set_rows",):
+            getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P, P]
+        for name in ("ggml_cpy", "ggml_get_rows"):
+            getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P]
+        base.ggml_cont.restype, base.ggml_cont.argtypes = P, [P, P]
+        for name in ("ggml_soft_max_ext", "ggml_soft_max_ext_inplace"):
+            getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P, C.c_float, C.c_float]
         for name in ("ggml_rope_ext", "ggml_rope_ext_inplace"):
             getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P, P, C.c_int, C.c_int, C.c_int] + [C.c_float] * 6
         cpu.ggml_cpu_init.restype, cpu.ggml_cpu_init.argtypes = None, []
@@ -101,7 +115,7 @@ def _graph(nbytes, build):
     """one context, one graph of the node build(base, ctx) returns, one thread; build's second result says what to read back (a list of
     (tensor, shape, dtype)); returns those arrays"""
     base, cpu = libs()
-    mem = nbytes + 16 * base.ggml_tensor_overhead() + base.ggml_graph_overhead() + (1 << 16)
+    mem = nbytes + 32 * base.ggml_tensor_overhead() + base.ggml_graph_overhead() + (1 << 16)
     ctx = base.ggml_init(_InitParams(mem, None, False))
     assert ctx
     try:
@@ -183,6 +197,137 @@ def rope(parent, view_ne, view_nb, view_offset, pos, ff, params, inplace):
     else:
         result = outs[1]
     return result, after
+
+
+# ---- SET_ROWS, CPY / CONT, GET_ROWS, SOFT_MAX with a mask ----------------------------------------------------------------------------
+def row_bytes(type_, ne0):
+    """ggml_row_size"""
+    size, blck = _BLOCK[type_]
+    assert ne0 % blck == 0, (type_, ne0)
+    return size * (ne0 // blck)
+
+
+class View:
+    """ggml_view_4d(parent, ne, nb[1..3], offset), then ggml_permute(axes) when axes is given (ggml_transpose for "transpose"): the description the
+    reference, the oracle and the device tensors are all built from.  nb defaults to dense rows of `ne`"""
+
+    def __init__(self, type_, ne, nb=None, offset=0, axes=None):
+        self.type = type_
+        self.ne = [int(v) for v in ne] + [1] * (4 - len(ne))
+        if nb is None:
+            nb = [_BLOCK[type_][0], row_bytes(type_, self.ne[0])]
+            nb += [nb[1] * self.ne[1], nb[1] * self.ne[1] * self.ne[2]]
+        self.nb = [int(v) for v in nb]
+        assert len(self.nb) == 4 and self.nb[0] == _BLOCK[type_][0]
+        self.offset, self.axes = int(offset), axes
+
+    def final(self):
+        """(ne, nb) after the permutation: dimension i of the view becomes dimension axes[i] of the result (ggml_permute)"""
+        axes = (1, 0, 2, 3) if self.axes == "transpose" else self.axes
+        if axes is None:
+            return list(self.ne), list(self.nb)
+        ne, nb = [0] * 4, [0] * 4
+        for i, a in enumerate(axes):
+            ne[a], nb[a] = self.ne[i], self.nb[i]
+        return ne, nb
+
+    def nelements(self):
+        return int(np.prod(self.ne))
+
+    def __repr__(self):
+        return f"View({self.type}, {self.ne}, {self.nb}, {self.offset}, {self.axes})"
+
+
+def _bytes(a):
+    return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+
+
+def _parent(base, ctx, type_, raw):
+    """a 1-D tensor of `type_` over a copy of the bytes `raw`: the buffer the views are cut from"""
+    size, blck = _BLOCK[type_]
+    assert raw.nbytes % size == 0, (type_, raw.nbytes)
+    t = base.ggml_new_tensor_1d(ctx, type_, raw.nbytes // size * blck)
+    C.memmove(base.ggml_get_data(t), raw.ctypes.data, raw.nbytes)
+    return t
+
+
+def _view(base, ctx, parent, v):
+    t = base.ggml_view_4d(ctx, parent, v.ne[0], v.ne[1], v.ne[2], v.ne[3], v.nb[1], v.nb[2], v.nb[3], v.offset)
+    if v.axes == "transpose":
+        t = base.ggml_transpose(ctx, t)
+    elif v.axes is not None:
+        t = base.ggml_permute(ctx, t, *v.axes)
+    return t
+
+
+def set_rows(dst0, dst_view, src, src_view, idx):
+    """ggml_set_rows(dst, src, idx).  dst0: the bytes of the destination's whole buffer; dst_view: the destination inside it (F32, F16 or Q8_0; a
+    view at an offset with padded rows, or the whole buffer); src: the float32 buffer the source is a ggml_view_4d of (src_view; rows may be
+    padded: nb[1] > ne0 * 4); idx: a dense int32 or int64 array of 1 to 3 dimensions (numpy order), which broadcasts over ne[2] and ne[3].
+    Returns the whole destination buffer afterwards, as bytes"""
+    dst0, src = _bytes(dst0), np.ascontiguousarray(src, np.float32).reshape(-1)
+    assert idx.dtype in (np.int32, np.int64) and 1 <= idx.ndim <= 3
+    idx = np.ascontiguousarray(idx)
+    it = GGML_TYPE_I64 if idx.dtype == np.int64 else GGML_TYPE_I32
+
+    def build(base, ctx):
+        d = _parent(base, ctx, dst_view.type, dst0)
+        s = _parent(base, ctx, GGML_TYPE_F32, _bytes(src))
+        out = base.ggml_set_rows(ctx, _view(base, ctx, d, dst_view), _view(base, ctx, s, src_view), _new(base, ctx, idx, it))
+        return out, [(d, dst0.shape, np.uint8)]
+    return _graph(dst0.nbytes + src.nbytes + idx.nbytes + (1 << 16), build)[0]
+
+
+def cpy(src0, src_view, dst0, dst_view):
+    """ggml_cpy(src, dst) between two views of two buffers given as bytes; dst0 None: ggml_cont(src), a dense tensor of the permuted view's shape.
+    Returns the destination's whole buffer afterwards, as bytes"""
+    src0 = _bytes(src0)
+    dst0 = None if dst0 is None else _bytes(dst0)
+    ne, _ = src_view.final()
+    n_out = row_bytes(src_view.type, ne[0]) * ne[1] * ne[2] * ne[3] if dst0 is None else dst0.nbytes
+
+    def build(base, ctx):
+        s = _view(base, ctx, _parent(base, ctx, src_view.type, src0), src_view)
+        if dst0 is None:
+            out = base.ggml_cont(ctx, s)
+            return out, [(out, (n_out,), np.uint8)]
+        d = _parent(base, ctx, dst_view.type, dst0)
+        out = base.ggml_cpy(ctx, s, _view(base, ctx, d, dst_view))
+        return out, [(d, dst0.shape, np.uint8)]
+    return _graph(src0.nbytes + n_out + (1 << 20), build)[0]
+
+
+def get_rows(table, type_, ne, idx0, idx_view):
+    """ggml_get_rows(table, idx): table: the bytes of a dense tensor of `type_` and shape ne [ne0, rows, ne2, ne3]; idx: an I32 view (1 to 3
+    dimensions, idx.ne[1] == ne2, idx.ne[2] == ne3: the batched form) of the int32 buffer idx0.  Returns float32 [idx.ne[2], idx.ne[1], idx.ne[0], ne0]"""
+    table, idx0 = _bytes(table), np.ascontiguousarray(idx0, np.int32).reshape(-1)
+    ne = [int(v) for v in ne] + [1] * (4 - len(ne))
+    ine, _ = idx_view.final()
+    shape = (ine[2], ine[1], ine[0], ne[0])
+
+    def build(base, ctx):
+        t = base.ggml_new_tensor_4d(ctx, type_, *ne)
+        assert row_bytes(type_, ne[0]) * ne[1] * ne[2] * ne[3] == table.nbytes
+        C.memmove(base.ggml_get_data(t), table.ctypes.data, table.nbytes)
+        out = base.ggml_get_rows(ctx, t, _view(base, ctx, _parent(base, ctx, GGML_TYPE_I32, _bytes(idx0)), idx_view))
+        return out, [(out, shape, np.float32)]
+    return _graph(table.nbytes + idx0.nbytes + 4 * int(np.prod(shape)) + (1 << 16), build)[0]
+
+
+def soft_max_ext(x, mask, scale, inplace=False):
+    """ggml_soft_max_ext(x, mask, scale, max_bias = 0) (or its _inplace form): x float32 [ne3, ne2, ne1, ne0]; mask float32 or float16, dense, with
+    mask.ne[0] == ne0, mask.ne[1] >= ne1 and ne[2], ne[3] dividing x's.  The shape of x"""
+    x = np.ascontiguousarray(x, np.float32)
+    assert mask.dtype in (np.float32, np.float16)
+    mask = np.ascontiguousarray(mask)
+    mt = GGML_TYPE_F16 if mask.dtype == np.float16 else GGML_TYPE_F32
+
+    def build(base, ctx):
+        a = _new(base, ctx, x)
+        ctor = base.ggml_soft_max_ext_inplace if inplace else base.ggml_soft_max_ext
+        d = ctor(ctx, a, _new(base, ctx, mask, mt), C.c_float(scale), C.c_float(0.0))
+        return d, [(d, x.shape, np.float32)]
+    return _graph(2 * x.nbytes + mask.nbytes + 4 * (x.shape[-1] + 64) + (1 << 16), build)[0]
 
 
 def gelu_tables():
