@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(256) k_attn_long_scores(const float * __restri
     TS(0);
     __shared__ float qs[R2 * HD];          // the group's query heads after RoPE, rounded to fp16 (src1 of K.Q)
     __shared__ float knew[HD], vnew[HD];   // the new k (after RoPE) and v, rounded to fp16 like the cache
-    constexpr int half = HD / 2, off = MODE == 0 ? 1 : half, U = 4;
+    constexpr int half = HD / 2, off = rope_pair(MODE, 0, half).off, U = 4;
     const int g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int KD = nkv * HD, QD = nh * HD;
     const int pos = uniform_load_i32_(pos_dev), n_kv = pos + 1;
@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(256) k_attn_long_scores(const float * __restri
     load_rows(i_lo + wave * RPI, cur);
 
     for (int t = tid; t < (R2 + 1) * half; t += 256) {          // pairs of the r2 query heads, then of k
-        const int which = t / half, i = t - which * half, ic = MODE == 0 ? 2 * i : i;
+        const int which = t / half, i = t - which * half, ic = rope_pair(MODE, i, half).ic;
         const float * x = which < R2 ? qkv + (g * R2 + which) * HD : qkv + QD + g * HD;
         const float x0 = x[ic], x1 = x[ic + off], c = rope_cs[2 * i], s_ = rope_cs[2 * i + 1];
         const float y0 = rope_rot_a(x0, x1, c, s_), y1 = rope_rot_b(x0, x1, c, s_);
@@ -153,17 +153,11 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax(const int32_t * __re
         float e[8];
 #pragma unroll
         for (int l = 0; l < 8; l++) { e[l] = ggml_expf_poly(sc[gi + l] - mx); sc[gi + l] = e[l]; }
-        const float a0 = e[0] + e[4], a1 = e[1] + e[5], a2 = e[2] + e[6], a3 = e[3] + e[7];
-        gsum[gi >> 3] = (a0 + a2) + (a1 + a3);
+        gsum[gi >> 3] = soft_group8_sum(e);
     }
     __syncthreads();
     if (wave == 0) {
-        double sum = 0.0;
-        for (int gq = lane; gq < (nv >> 3); gq += 64) sum += (double) gsum[gq];
-        if (lane == 0) for (int i = nv; i < n_kv; i++) { const float e = libm_expf(sc[i] - mx); sc[i] = e; sum += (double) e; }
-        sum = wave_sum_d(sum);
-        double rinv = 1.0 / sum;                                      // (ORDER: soft_total_order_safe, common.h)
-        if (__builtin_expect(!soft_total_order_safe(rinv, n_kv >> 3), 0)) { wave_lds_fence(); rinv = 1.0 / soft_sum_serial_groups(gsum, nv >> 3, sc, nv, n_kv); }
+        const double rinv = soft_total_rinv_groups(gsum, nv >> 3, sc, nv, n_kv, mx, n_kv >> 3, lane);
         if (lane == 0) red_d[0] = rinv;
     }
     __syncthreads();
@@ -301,17 +295,11 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
         float e[8] = { ggml_expf_poly(s0.x - mx), ggml_expf_poly(s0.y - mx), ggml_expf_poly(s0.z - mx), ggml_expf_poly(s0.w - mx),
                        ggml_expf_poly(s1.x - mx), ggml_expf_poly(s1.y - mx), ggml_expf_poly(s1.z - mx), ggml_expf_poly(s1.w - mx) };
         *(f32x4 *)(ex + gi) = f32x4{e[0], e[1], e[2], e[3]}; *(f32x4 *)(ex + gi + 4) = f32x4{e[4], e[5], e[6], e[7]};
-        const float a0 = e[0] + e[4], a1 = e[1] + e[5], a2 = e[2] + e[6], a3 = e[3] + e[7];
-        gsum[gi >> 3] = (a0 + a2) + (a1 + a3);
+        gsum[gi >> 3] = soft_group8_sum(e);
     }
     __syncthreads();
     if (wave == 0) {
-        double sum = 0.0;
-        for (int gq = lane; gq < (nv >> 3); gq += 64) sum += (double) gsum[gq];
-        if (lane == 0) for (int i = nv; i < n_kv; i++) { const float e = libm_expf(ex[i] - mx); ex[i] = e; sum += (double) e; }
-        sum = wave_sum_d(sum);
-        double rinv = 1.0 / sum;                                      // (ORDER: soft_total_order_safe, common.h)
-        if (__builtin_expect(!soft_total_order_safe(rinv, n_kv >> 3), 0)) { wave_lds_fence(); rinv = 1.0 / soft_sum_serial_groups(gsum, nv >> 3, ex, nv, n_kv); }
+        const double rinv = soft_total_rinv_groups(gsum, nv >> 3, ex, nv, n_kv, mx, n_kv >> 3, lane);
         if (lane == 0) red_d[0] = rinv;
     }
     __syncthreads();

@@ -347,6 +347,12 @@ __device__ __forceinline__ float norm_variance(double V, int64_t n, float mean, 
 // workgroup barrier for data exchanged through LDS only: __syncthreads() also drains vmcnt, i.e. waits for every global load in flight --
 // which is exactly what a latency-bound kernel prefetches ACROSS its phases.  LDS operations of a wave complete in order: lgkmcnt(0) + s_barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// compiler-level ordering of the wave's own LDS records (the LDS executes one wave's DS operations in order)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // load through the scalar cache (p must be wave-uniform; the data must not have been written by this kernel before).
 // Scalar loads have their own counter (lgkmcnt), so they do not serialise against outstanding vector-memory prefetches.
@@ -387,6 +393,27 @@ static __device__ __noinline__ void rope_cos_sin(float theta, float * c, float *
 // rounded x1 product (determined bit for bit against libggml-cpu.so; the oracle states the same)
 __device__ __forceinline__ float rope_rot_a(float x0, float x1, float c, float s) { return __builtin_fmaf(x0, c, -(x1 * s)); }
 __device__ __forceinline__ float rope_rot_b(float x0, float x1, float c, float s) { return __builtin_fmaf(x0, s, x1 * c); }
+// ---- the RoPE table, stated ONCE: a kernel that needs the angle, an entry, a table or a pair's addresses calls these; it does not restate them.
+// theta of pair i at position pos: ITERATED fp32 multiplication by theta_scale (ggml_rope_cache_init, ops.cpp:5613-5627) -- powf(theta_scale, i) rounds differently.
+__device__ __forceinline__ float rope_theta(int pos, int i, float theta_scale) {
+    float theta = (float) pos;
+    for (int k = 0; k < i; k++) theta *= theta_scale;
+    return theta;
+}
+// the PLAIN entry (no frequency factors, freq_scale 1, no YaRN, attn_factor 1: rope_yarn, ops.cpp:5596-5611, multiplies cos and sin by an mscale of 1.0f there, which changes
+// no bit; the compiler had folded the `* 1.0f` away in the four kernels that wrote it out).  k_rope (ops.hip) takes rope_theta and keeps its own frequency-factor and YaRN lines.
+__device__ __forceinline__ void rope_entry(int pos, int i, float theta_scale, float * c, float * s) { rope_cos_sin(rope_theta(pos, i, theta_scale), c, s); }
+// cs[2 i] = cos, cs[2 i + 1] = sin for the pairs i = first, first + step, ... below half
+__device__ __forceinline__ void rope_table_fill(float * cs, int pos, int half, float theta_scale, int first, int step) {
+    for (int i = first; i < half; i += step) {
+        float c, s;
+        rope_entry(pos, i, theta_scale, &c, &s);
+        cs[2*i] = c; cs[2*i + 1] = s;
+    }
+}
+// the two elements pair i rotates: x[ic] and x[ic + off] -- adjacent in mode 0 (GGML_ROPE_TYPE_NORMAL), half a rotated row apart otherwise (NEOX), ops.cpp:5700-5718
+struct rope_pair_t { int ic, off; };
+__device__ __forceinline__ constexpr rope_pair_t rope_pair(int mode, int i, int half) { return rope_pair_t{ mode == 0 ? 2*i : i, mode == 0 ? 1 : half }; }
 
 // one lane of the reference's AVX2 ggml_v_expf (ggml-cpu/vec.h:1230-1267), op for op, so that
 // soft_max / SiLU agree with the CPU path to the last bit wherever the CPU takes its vector body.
@@ -421,14 +448,18 @@ __device__ __forceinline__ bool soft_total_order_safe(double rinv, int m_terms) 
     const int low = (int)((unsigned long long) __double_as_longlong(rinv) & 0x1fffffffull) - 0x10000000;
     return !SOFT_FORCE_SERIAL && (low < 0 ? -low : low) > m_terms + 24;
 }
+// the float sum of one group of 8 exponentials, as the AVX2 body of ggml_vec_soft_max_f32 adds it up (vec.cpp:558-567: upper + lower half, movehl, movehdup).
+// Every soft_max kernel forms its group sums through this; none restates the tree.
+__device__ __forceinline__ float soft_group8_sum(float e0, float e1, float e2, float e3, float e4, float e5, float e6, float e7) {
+    const float a0 = e0 + e4, a1 = e1 + e5, a2 = e2 + e6, a3 = e3 + e7;
+    return (a0 + a2) + (a1 + a3);
+}
+__device__ __forceinline__ float soft_group8_sum(const float * e) { return soft_group8_sum(e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7]); }
 // the total in the reference's order from the exponentials e[0 .. n) (any address space): lane 0 of the calling wave, the result broadcast
 static __device__ __noinline__ double soft_sum_serial(const float * e, int nv, int n) {
     double sum = 0.0;
     if ((threadIdx.x & 63) == 0) {
-        for (int gi = 0; gi < nv; gi += 8) {
-            const float a0 = e[gi] + e[gi + 4], a1 = e[gi + 1] + e[gi + 5], a2 = e[gi + 2] + e[gi + 6], a3 = e[gi + 3] + e[gi + 7];
-            sum += (double)((a0 + a2) + (a1 + a3));
-        }
+        for (int gi = 0; gi < nv; gi += 8) sum += (double) soft_group8_sum(e + gi);
         for (int i = nv; i < n; i++) sum += (double) e[i];
     }
     return lane_d(sum, 0);
@@ -441,6 +472,31 @@ static __device__ __noinline__ double soft_sum_serial_groups(const float * gs, i
         for (int i = nv; i < n; i++) sum += (double) e[i];
     }
     return lane_d(sum, 0);
+}
+// 1 / total, by the ONE wave that owns the total, from the exponentials e[0 .. n) already in LDS (nv = n & ~7; 16-byte aligned): lane l adds the groups l, l + 64, ...
+// in double, lane 0 the n mod 8 leftovers behind its groups, a DPP tree over the lanes; redone serially where the order could show (ORDER, above).  Every lane returns it.
+__device__ __forceinline__ double soft_total_rinv(const float * e, int nv, int n, int lane) {
+    double sum = 0.0;
+    for (int gi = lane * 8; gi < nv; gi += 64 * 8) {
+        const f32x4 lo = *(const f32x4 *)(e + gi), up = *(const f32x4 *)(e + gi + 4);
+        sum += (double) soft_group8_sum(lo.x, lo.y, lo.z, lo.w, up.x, up.y, up.z, up.w);
+    }
+    if (lane == 0) for (int i = nv; i < n; i++) sum += (double) e[i];
+    sum = wave_sum_d(sum);
+    double rinv = 1.0 / sum;
+    if (__builtin_expect(!soft_total_order_safe(rinv, n >> 3), 0)) rinv = 1.0 / soft_sum_serial(e, nv, n);
+    return rinv;
+}
+// the same from the float group sums gs[0 .. ng) other waves left in LDS.  The leftovers e[nv .. n) still hold scores: lane 0 exponentiates them here (expf, as
+// the reference's scalar tail does) and stores them back, hence the fence in front of the serial pass.  m_terms: the groups of the reference's sum (masked ones included).
+__device__ __forceinline__ double soft_total_rinv_groups(const float * gs, int ng, float * e, int nv, int n, float mx, int m_terms, int lane) {
+    double sum = 0.0;
+    for (int gq = lane; gq < ng; gq += 64) sum += (double) gs[gq];
+    if (lane == 0) for (int i = nv; i < n; i++) { const float ev = libm_expf(e[i] - mx); e[i] = ev; sum += (double) ev; }
+    sum = wave_sum_d(sum);
+    double rinv = 1.0 / sum;
+    if (__builtin_expect(!soft_total_order_safe(rinv, m_terms), 0)) { wave_lds_fence(); rinv = 1.0 / soft_sum_serial_groups(gs, ng, e, nv, n); }
+    return rinv;
 }
 
 // SiLU as ggml_vec_silu_f32 computes it (vec.cpp:396-431): the AVX2 polynomial for the elements below n & ~7 of a row, expf for the leftovers
@@ -456,8 +512,7 @@ __device__ __forceinline__ void wave_soft_max_plain(const float * x, float * y, 
         float e[8];
 #pragma unroll
         for (int l = 0; l < 8; l++) { e[l] = ggml_expf_poly(x[g + l] - mx); y[g + l] = e[l]; }
-        const float a0 = e[0] + e[4], a1 = e[1] + e[5], a2 = e[2] + e[6], a3 = e[3] + e[7];
-        sum += (double)((a0 + a2) + (a1 + a3));
+        sum += (double) soft_group8_sum(e);
     }
     if (lane == 0) for (int i = nv; i < n; i++) { const float e = libm_expf(x[i] - mx); y[i] = e; sum += (double) e; }
     sum = wave_sum_d(sum);
@@ -486,6 +541,42 @@ __device__ __forceinline__ void top_k_row(const float * x, int n, int k, int32_t
 }
 __device__ __forceinline__ float silu_poly(float x) { return x / (1.0f + ggml_expf_poly(0.0f - x)); }
 __device__ __forceinline__ float silu_any(float x, bool body) { return body ? silu_poly(x) : x / (1.0f + libm_expf(-x)); }
+// ---- the greedy sampler's reduce, stated ONCE (std::max_element, src/models.cpp:676-690: the FIRST maximum).  (value, index) pairs under a total order: the larger
+// value wins, the lower index on ties, NaN never wins (both comparisons are false), so how the values are split over lanes, waves and workgroups does not matter.
+// A reduce starts from (-INFINITY, ARGMAX_NO_INDEX) and ends in argmax_id: nothing compared greater than -inf (all -inf, all NaN) -> id 0.
+#define ARGMAX_NO_INDEX 0x7fffffff
+__device__ __forceinline__ void argmax_combine(float & best, int & idx, float ov, int oi) {
+    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+}
+__device__ __forceinline__ int argmax_id(int idx) { return idx == ARGMAX_NO_INDEX ? 0 : idx; }
+// this thread's share x[lo + first], x[lo + first + step], ... of the slice [lo, hi): indices ascend, so `>` alone keeps the first maximum
+__device__ __forceinline__ void argmax_scan(const float * __restrict__ x, int lo, int hi, int first, int step, float & best, int & idx) {
+    for (int i = lo + first; i < hi; i += step) { const float v = x[i]; if (v > best) { best = v; idx = i; } }
+}
+// this thread's share of np (value, index) partials of an earlier stage
+__device__ __forceinline__ void argmax_scan_partials(const float * __restrict__ pv, const int * __restrict__ pi, int np, int first, int step, float & best, int & idx) {
+    for (int i = first; i < np; i += step) argmax_combine(best, idx, pv[i], pi[i]);
+}
+__device__ __forceinline__ void argmax_wave(float & best, int & idx) {                  // butterfly: every lane ends with the wave's pair
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64); argmax_combine(best, idx, ov, oi); }
+}
+// the waves' pairs through the caller's LDS slots (NW floats, NW ints; free on entry), thread 0 combines them in wave order: the workgroup's pair, in thread 0 ONLY.
+// Contains a barrier.  (lane, wave: the caller's own, a kernel that holds its wave index in a scalar register keeps it there)
+template <int NW> __device__ __forceinline__ void argmax_slots(float & best, int & idx, float * bv, int * bi, int lane, int wave) {
+    if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) for (int w = 1; w < NW; w++) argmax_combine(best, idx, bv[w], bi[w]);
+}
+template <int NW> __device__ __forceinline__ void argmax_block(float & best, int & idx, float * bv, int * bi) {
+    argmax_wave(best, idx);
+    argmax_slots<NW>(best, idx, bv, bi, threadIdx.x & 63, threadIdx.x >> 6);
+}
+// thread 0 hands the token to the next step (and to a host that polls for it: visible system-wide before anything later)
+__device__ __forceinline__ void argmax_publish_token(int id, int32_t * tok_dev, int32_t * tok_host) {
+    tok_dev[0] = id;
+    if (tok_host) { tok_host[0] = id; __threadfence_system(); }
+}
 // ---- workgroup -> output tile of a prefill GEMM, L2-aware.  A 1-D grid of TM * TN workgroups (TM token tiles, TN weight-row tiles).  The dispatcher places workgroup
 // b on XCD b % 8 (private 4 MB L2s): every XCD gets one CONTIGUOUS chunk of the logical tile order (bijective for any count), and the logical order walks a group
 // of GM token tiles x all row tiles with the token tile fastest, so the ~64 workgroups an XCD runs concurrently share GM activation tiles (each re-read from HBM

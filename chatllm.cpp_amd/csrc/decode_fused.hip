@@ -58,13 +58,13 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
     float * qs = sm; float * knew = sm + hd; float * vnew = sm + 2 * hd; float * sc = sm + 3 * hd;
 
     // ---- (1) this head's projections: one (q or k) pair or one v element per thread, loads issued before anything waits ----
-    const int off = mode == 0 ? 1 : half;
+    const int off = rope_pair(mode, 0, half).off;
     const float * qh = qkv + h * hd; const float * kh = qkv + QD + g * hd; const float * vh = qkv + QD + KD + g * hd;
     float px0 = 0.0f, px1 = 0.0f, pv = 0.0f;
     const bool pair_fast = ROPE && 2 * half + hd <= nthr;             // every pair / v element has its own thread
     if (pair_fast) {
         if (tid < 2 * half) {
-            const int which = tid / half, i = tid % half, ic = mode == 0 ? 2*i : i;
+            const int which = tid / half, i = tid % half, ic = rope_pair(mode, i, half).ic;
             const float * x = which == 0 ? qh : kh;
             px0 = x[ic]; px1 = x[ic + off];
         } else if (tid < 2 * half + hd) pv = vh[tid - 2 * half];
@@ -80,28 +80,19 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
     if (ROPE) {
         if (pair_fast) {
             if (tid < 2 * half) {
-                const int which = tid / half, i = tid % half, ic = mode == 0 ? 2*i : i;
-                float theta = (float) pos;
-                for (int k = 0; k < i; k++) theta *= theta_scale;
+                const int which = tid / half, i = tid % half, ic = rope_pair(mode, i, half).ic;
                 float c, s_;
-                rope_cos_sin(theta, &c, &s_);
-                c = c * 1.0f; s_ = s_ * 1.0f;
+                rope_entry(pos, i, theta_scale, &c, &s_);
                 const float y0 = rope_rot_a(px0, px1, c, s_), y1 = rope_rot_b(px0, px1, c, s_);
                 float * o = which == 0 ? qs : knew;
                 o[ic] = h2f(f2h(y0)); o[ic + off] = h2f(f2h(y1));         // q: src1 of K.Q is rounded to fp16; k: the cache is fp16
             } else if (tid < 2 * half + hd) vnew[tid - 2 * half] = h2f(f2h(pv));
         } else {
             float * cs = sc;                                            // scores are not live yet
-            for (int i = tid; i < half; i += nthr) {
-                float theta = (float) pos;
-                for (int k = 0; k < i; k++) theta *= theta_scale;
-                float c, s_;
-                rope_cos_sin(theta, &c, &s_);
-                cs[2*i] = c * 1.0f; cs[2*i + 1] = s_ * 1.0f;
-            }
+            rope_table_fill(cs, pos, half, theta_scale, tid, nthr);
             __syncthreads();
             for (int t = tid; t < 2 * half; t += nthr) {
-                const int which = t / half, i = t % half, ic = mode == 0 ? 2*i : i;
+                const int which = t / half, i = t % half, ic = rope_pair(mode, i, half).ic;
                 const float c = cs[2*i], s_ = cs[2*i + 1];
                 const float * x = which == 0 ? qh : kh;
                 const float x0 = x[ic], x1 = x[ic + off];
@@ -152,16 +143,7 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
     for (int i = tid; i < n_kv; i += nthr) sc[i] = i < nv ? ggml_expf_poly(sc[i] - mx) : libm_expf(sc[i] - mx);
     __syncthreads();
     if (wave == 0) {
-        double sum = 0.0;
-        for (int gi = lane * 8; gi < nv; gi += 64 * 8) {
-            const f32x4 lo = *(const f32x4 *)(sc + gi), up = *(const f32x4 *)(sc + gi + 4);
-            const float a0 = lo.x + up.x, a1 = lo.y + up.y, a2 = lo.z + up.z, a3 = lo.w + up.w;
-            sum += (double)((a0 + a2) + (a1 + a3));
-        }
-        if (lane == 0) for (int i = nv; i < n_kv; i++) sum += (double) sc[i];
-        sum = wave_sum_d(sum);
-        double rinv = 1.0 / sum;                                      // (ORDER: soft_total_order_safe, common.h)
-        if (__builtin_expect(!soft_total_order_safe(rinv, n_kv >> 3), 0)) rinv = 1.0 / soft_sum_serial(sc, nv, n_kv);
+        const double rinv = soft_total_rinv(sc, nv, n_kv, lane);
         if (lane == 0) red_d[0] = rinv;
     }
     __syncthreads();
@@ -204,13 +186,7 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
 // Arithmetic and summation order are those of the general kernel (= of the unfused graph nodes).
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) k_rope_table(const int32_t * __restrict__ pos_dev, int half, float theta_scale, float * __restrict__ cs) {
-    for (int i = threadIdx.x; i < half; i += 64) {
-        float theta = (float) pos_dev[0];
-        for (int k = 0; k < i; k++) theta *= theta_scale;        // iterated fp32 multiplication, ops.cpp:5639-5650
-        float c, s_;
-        rope_cos_sin(theta, &c, &s_);
-        cs[2*i] = c * 1.0f; cs[2*i + 1] = s_ * 1.0f;
-    }
+    rope_table_fill(cs, pos_dev[0], half, theta_scale, threadIdx.x, 64);
 }
 int launch_rope_table(hipStream_t st, const int32_t * pos_dev, int hd, float freq_base, float * cs) {
     hipLaunchKernelGGL(k_rope_table, dim3(1), dim3(64), 0, st, pos_dev, hd / 2, powf(freq_base, -2.0f / hd), cs);
@@ -233,7 +209,7 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
     extern __shared__ __attribute__((aligned(16))) float sm[];       // [HD] q (fp16-rounded) | [HD] new k | [HD] new v | [n_kv] scores
     __shared__ float  red_f[16];
     __shared__ uint64_t etab_s[32];                                   // glibc's exp2f table for the soft_max's n mod 8 leftovers (see (5))
-    constexpr int half = HD / 2, off = MODE == 0 ? 1 : half, U = 4;
+    constexpr int half = HD / 2, off = rope_pair(MODE, 0, half).off, U = 4;
     const int r2 = gridDim.x, g = blockIdx.y, h = g * r2 + blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int KD = nkv * HD, QD = nh * HD;
@@ -242,7 +218,7 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
     // ---- (1) this head's projections + the cos/sin of its pairs: loads issued before anything waits ----
     float px0 = 0.0f, px1 = 0.0f, pc = 0.0f, ps = 0.0f;
     const bool is_pair = tid < 2 * half, is_v = !is_pair && tid < 2 * half + HD;
-    const int which = tid >= half ? 1 : 0, pi = tid - which * half, ic = MODE == 0 ? 2 * pi : pi;
+    const int which = tid >= half ? 1 : 0, pi = tid - which * half, ic = rope_pair(MODE, pi, half).ic;
     if (is_pair) {
         const float * x = which == 0 ? qkv + h * HD : qkv + QD + g * HD;
         px0 = x[ic]; px1 = x[ic + off];
@@ -365,17 +341,7 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
     }
     lds_barrier();
     if (wave == 0) {
-        double sum = 0.0;
-        for (int gi = lane * 8; gi < nv; gi += 64 * 8) {
-            const f32x4 lo = *(const f32x4 *)(sc + gi), up = *(const f32x4 *)(sc + gi + 4);
-            const float a0 = lo.x + up.x, a1 = lo.y + up.y, a2 = lo.z + up.z, a3 = lo.w + up.w;
-            sum += (double)((a0 + a2) + (a1 + a3));
-        }
-        if (lane == 0) for (int i = nv; i < n_kv; i++) sum += (double) sc[i];
-        sum = wave_sum_d(sum);
-        // (ORDER: a tree, the reference adds serially -- proved not to matter per row, else redone serially: soft_total_order_safe, common.h)
-        double rinv = 1.0 / sum;
-        if (__builtin_expect(!soft_total_order_safe(rinv, n_kv >> 3), 0)) rinv = 1.0 / soft_sum_serial(sc, nv, n_kv);
+        const double rinv = soft_total_rinv(sc, nv, n_kv, lane);
         if (lane == 0) red_f[0] = (float) rinv;                       // (every thread read the maxima before the barrier above)
     }
     lds_barrier();
@@ -524,41 +490,40 @@ extern "C" int cllm_op_rope_kv_attn_decode(void * stream, const float * qkv, con
 // greedy sampler in two short launches (a single workgroup scanning 128K logits took 43 us):
 //   stage 1: 256 workgroups each reduce a contiguous slice to (value, index), first maximum wins
 //   stage 2: one workgroup reduces the 256 partials in slice order and advances the device-side loop state
-__device__ __forceinline__ void argmax_combine(float & best, int & idx, float ov, int oi) {
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+// (the order, the reduce and the token's publication: the argmax_* helpers, common.h)
+// the slice of workgroup b of a 256-thread grid, reduced: (value, index) in thread 0
+__device__ __forceinline__ void argmax_slice_256(const float * __restrict__ x, int n, float & best, int & idx, float * bv, int * bi) {
+    const int per = (n + gridDim.x - 1) / gridDim.x;
+    const int lo = blockIdx.x * per, hi = min(n, lo + per);
+    best = -INFINITY; idx = ARGMAX_NO_INDEX;
+    argmax_scan(x, lo, hi, threadIdx.x, 256, best, idx);
+    argmax_block<4>(best, idx, bv, bi);
+}
+// np partials reduced by one workgroup of 64 NW threads: the id in thread 0
+template <int NW> __device__ __forceinline__ int argmax_final_id(const float * __restrict__ pv, const int * __restrict__ pi, int np, float * bv, int * bi) {
+    float best = -INFINITY; int idx = ARGMAX_NO_INDEX;
+    argmax_scan_partials(pv, pi, np, threadIdx.x, 64 * NW, best, idx);
+    argmax_block<NW>(best, idx, bv, bi);
+    return argmax_id(idx);
+}
+// thread 0 advances the runner's greedy loop: the next step's input token and position, the id into the output ring
+__device__ __forceinline__ void argmax_advance_loop(int id, int pos_next, int32_t * tok_dev, int32_t * pos_dev, int32_t * out_ring, int32_t * counter) {
+    tok_dev[0] = id;
+    pos_dev[0] = pos_next;
+    out_ring[counter[0]] = id;
+    counter[0] = counter[0] + 1;
 }
 __global__ void __launch_bounds__(256) k_argmax_partial(const float * __restrict__ x, int n, float * __restrict__ pv, int * __restrict__ pi) {
     __shared__ float bv[4]; __shared__ int bi[4];
-    const int per = (n + gridDim.x - 1) / gridDim.x;
-    const int lo = blockIdx.x * per, hi = min(n, lo + per);
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = lo + threadIdx.x; i < hi; i += 256) { const float v = x[i]; if (v > best) { best = v; idx = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) argmax_combine(best, idx, bv[w], bi[w]);
-        pv[blockIdx.x] = best; pi[blockIdx.x] = idx;
-    }
+    float best; int idx;
+    argmax_slice_256(x, n, best, idx, bv, bi);
+    if (threadIdx.x == 0) { pv[blockIdx.x] = best; pi[blockIdx.x] = idx; }
 }
 __global__ void __launch_bounds__(256) k_argmax_final(const float * __restrict__ pv, const int * __restrict__ pi, int np, int32_t * __restrict__ tok_dev,
                                                       int32_t * __restrict__ pos_dev, int32_t * __restrict__ out_ring, int32_t * __restrict__ counter) {
     __shared__ float bv[4]; __shared__ int bi[4];
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < np; i += 256) argmax_combine(best, idx, pv[i], pi[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) argmax_combine(best, idx, bv[w], bi[w]);
-        if (idx == 0x7fffffff) idx = 0;
-        tok_dev[0] = idx;                 // next step's input token
-        pos_dev[0] = pos_dev[0] + 1;      // and its position
-        out_ring[counter[0]] = idx;
-        counter[0] = counter[0] + 1;
-    }
+    const int id = argmax_final_id<4>(pv, pi, np, bv, bi);
+    if (threadIdx.x == 0) argmax_advance_loop(id, pos_dev[0] + 1, tok_dev, pos_dev, out_ring, counter);
 }
 // The second stage AND the head of the NEXT step in one launch (the runner's greedy loop: one workgroup is on the chip anyway): the token's embedding row (GET_ROWS,
 // dequant_elem: the bits of k_get_rows) into x_next and the cos / sin table of position pos + 1 (k_rope_table's code, by the last wave while thread 0 finishes the reduce).
@@ -570,29 +535,12 @@ __global__ void __launch_bounds__(1024) k_argmax_final_next(const float * __rest
     __shared__ float bv[16]; __shared__ int bi[16]; __shared__ int tok_s;
     const int tid = threadIdx.x;
     const int pos_next = pos_dev[0] + 1;              // (read by everybody BEFORE the barrier thread 0 stores behind)
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = tid; i < np; i += 1024) argmax_combine(best, idx, pv[i], pi[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    if ((tid & 63) == 0) { bv[tid >> 6] = best; bi[tid >> 6] = idx; }
-    __syncthreads();
+    const int id = argmax_final_id<16>(pv, pi, np, bv, bi);
     if (tid == 0) {
-        for (int w = 1; w < 16; w++) argmax_combine(best, idx, bv[w], bi[w]);
-        if (idx == 0x7fffffff) idx = 0;
-        tok_s = idx;
-        tok_dev[0] = idx;                 // next step's input token
-        pos_dev[0] = pos_next;            // and its position
-        out_ring[counter[0]] = idx;
-        counter[0] = counter[0] + 1;
+        tok_s = id;
+        argmax_advance_loop(id, pos_next, tok_dev, pos_dev, out_ring, counter);
     }
-    if (cs && tid >= 960)
-        for (int i = tid - 960; i < half; i += 64) {
-            float theta = (float) pos_next;
-            for (int k = 0; k < i; k++) theta *= theta_scale;        // iterated fp32 multiplication, ops.cpp:5639-5650
-            float c, s_;
-            rope_cos_sin(theta, &c, &s_);
-            cs[2*i] = c * 1.0f; cs[2*i + 1] = s_ * 1.0f;
-        }
+    if (cs && tid >= 960) rope_table_fill(cs, pos_next, half, theta_scale, tid - 960, 64);
     __syncthreads();
     const char * row = emb + (size_t) tok_s * emb_nb1;
     for (int c = tid; c < H; c += 1024) x_next[c] = dequant_elem(etype, row, c);
@@ -613,39 +561,22 @@ int launch_argmax_final_next(hipStream_t st, const float * part_v, const int * p
 __global__ void __launch_bounds__(256) k_argmax_publish(const float * __restrict__ pv, const int * __restrict__ pi, int np, int32_t * __restrict__ tok_dev,
                                                         int32_t * __restrict__ tok_host, int32_t * const * __restrict__ inc, int n_inc) {
     __shared__ float bv[4]; __shared__ int bi[4];
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < np; i += 256) argmax_combine(best, idx, pv[i], pi[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) argmax_combine(best, idx, bv[w], bi[w]);
-        if (idx == 0x7fffffff) idx = 0;
-        tok_dev[0] = idx;
-        if (tok_host) { tok_host[0] = idx; __threadfence_system(); }
-    }
+    const int id = argmax_final_id<4>(pv, pi, np, bv, bi);
+    if (threadIdx.x == 0) argmax_publish_token(id, tok_dev, tok_host);
     for (int i = threadIdx.x; i < n_inc; i += 256) inc[i][0] = inc[i][0] + 1;
 }
 // the same with ABSOLUTE values: every (pointer, value) record of set_table_dev[] is stored (no read-modify-write of memory the previous graph's later
 // nodes may have reused)
 struct argmax_set_rec { int32_t * ptr; int32_t val; int32_t pad; };
+__device__ __forceinline__ void argmax_store_recs(const argmax_set_rec * __restrict__ recs, int n_set) {
+    for (int i = threadIdx.x; i < n_set; i += 256) recs[i].ptr[0] = recs[i].val;
+}
 __global__ void __launch_bounds__(256) k_argmax_publish_set(const float * __restrict__ pv, const int * __restrict__ pi, int np, int32_t * __restrict__ tok_dev,
                                                             int32_t * __restrict__ tok_host, const argmax_set_rec * __restrict__ recs, int n_set) {
     __shared__ float bv[4]; __shared__ int bi[4];
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < np; i += 256) argmax_combine(best, idx, pv[i], pi[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) argmax_combine(best, idx, bv[w], bi[w]);
-        if (idx == 0x7fffffff) idx = 0;
-        tok_dev[0] = idx;
-        if (tok_host) { tok_host[0] = idx; __threadfence_system(); }
-    }
-    for (int i = threadIdx.x; i < n_set; i += 256) recs[i].ptr[0] = recs[i].val;
+    const int id = argmax_final_id<4>(pv, pi, np, bv, bi);
+    if (threadIdx.x == 0) argmax_publish_token(id, tok_dev, tok_host);
+    argmax_store_recs(recs, n_set);
 }
 extern "C" int cllm_op_argmax_set(void * stream, const float * logits, int64_t n, int32_t * tok_dev, int32_t * tok_host, const void * set_table_dev, int n_set, void * scratch) {
     if (!logits || n <= 0 || n > INT32_MAX || !tok_dev || !scratch || n_set < 0 || (n_set && !set_table_dev)) FAIL(CLLM_E_INVALID, "argmax_set: arguments");
@@ -671,16 +602,9 @@ __global__ void __launch_bounds__(256) k_snapshot_argmax_set(const snap_range * 
         if ((((uintptr_t) R.src | (uintptr_t) R.dst | R.bytes) & 15) == 0) { for (unsigned long long i = gid; i < R.bytes / 16; i += gsz) ((u32x4 *) R.dst)[i] = ((const u32x4 *) R.src)[i]; }
         else                                                               { for (unsigned long long i = gid; i < R.bytes / 4; i += gsz) ((uint32_t *) R.dst)[i] = ((const uint32_t *) R.src)[i]; }
     }
-    const int per = (n + gridDim.x - 1) / gridDim.x;
-    const int lo = blockIdx.x * per, hi = min(n, lo + per);
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = lo + tid; i < hi; i += 256) { const float v = x[i]; if (v > best) { best = v; idx = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    if ((tid & 63) == 0) { bv[tid >> 6] = best; bi[tid >> 6] = idx; }
-    __syncthreads();                                               // (also: every thread's copies and logit reads are issued and their values consumed)
+    float best; int idx;
+    argmax_slice_256(x, n, best, idx, bv, bi);                     // (its barrier also: every thread's copies and logit reads are issued and their values consumed)
     if (tid == 0) {
-        for (int w = 1; w < 4; w++) argmax_combine(best, idx, bv[w], bi[w]);
         __hip_atomic_store(pv + blockIdx.x, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(pi + blockIdx.x, idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence();                                           // this workgroup's stores (snapshot, partial) before its ticket
@@ -690,22 +614,17 @@ __global__ void __launch_bounds__(256) k_snapshot_argmax_set(const snap_range * 
     __syncthreads();
     if (!last_s) return;
     __threadfence();
-    best = -INFINITY; idx = 0x7fffffff;
-    for (int i = tid; i < (int) gridDim.x; i += 256)
+    best = -INFINITY; idx = ARGMAX_NO_INDEX;
+    for (int i = tid; i < (int) gridDim.x; i += 256)               // (argmax_scan_partials with coherent loads: other workgroups of THIS launch stored them)
         argmax_combine(best, idx, __hip_atomic_load(pv + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(pi + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_combine(best, idx, __shfl_xor(best, o, 64), __shfl_xor(idx, o, 64));
-    __syncthreads();
-    if ((tid & 63) == 0) { bv[tid >> 6] = best; bi[tid >> 6] = idx; }
-    __syncthreads();
+    argmax_wave(best, idx);
+    __syncthreads();                                               // (the first stage's slots are reused)
+    argmax_slots<4>(best, idx, bv, bi, tid & 63, tid >> 6);
     if (tid == 0) {
-        for (int w = 1; w < 4; w++) argmax_combine(best, idx, bv[w], bi[w]);
-        if (idx == 0x7fffffff) idx = 0;
-        tok_dev[0] = idx;
-        if (tok_host) { tok_host[0] = idx; __threadfence_system(); }
+        argmax_publish_token(argmax_id(idx), tok_dev, tok_host);
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // the next launch starts from zero
     }
-    for (int i = tid; i < n_set; i += 256) recs[i].ptr[0] = recs[i].val;
+    argmax_store_recs(recs, n_set);
 }
 // ranges_dev: n_ranges x { src, dst, bytes } (device table; bytes % 4 == 0); scratch: 4096 bytes of device memory, ZEROED by the caller before the first use (partials + ticket)
 extern "C" __attribute__((visibility("default")))

@@ -666,19 +666,10 @@ static int ensure_decode_graph(cllm_llama * m, bool long_ctx) {
 // ---- greedy decode loop (sampler = std::max_element, src/models.cpp:676-690: first maximum wins) ------------------
 __global__ void __launch_bounds__(1024) k_argmax(const float * __restrict__ x, int n, int32_t * __restrict__ out) {
     __shared__ float bv[16]; __shared__ int bi[16];
-    float best = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { const float v = x[i]; if (v > best) { best = v; idx = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++) if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        out[0] = idx == 0x7fffffff ? 0 : idx;
-    }
+    float best = -INFINITY; int idx = ARGMAX_NO_INDEX;                 // (one launch of 1024 threads; the reduce: the argmax_* helpers, common.h)
+    argmax_scan(x, 0, n, threadIdx.x, blockDim.x, best, idx);
+    argmax_block<16>(best, idx, bv, bi);
+    if (threadIdx.x == 0) out[0] = argmax_id(idx);
 }
 
 extern "C" int cllm_llama_decode_greedy(cllm_llama * m, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens_host) {

@@ -529,13 +529,13 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
 template <int HD, int MODE>
 __global__ void __launch_bounds__(HD) k_rope_kv_prep(const float * __restrict__ qkv, const int32_t * __restrict__ pos_dev, const float * __restrict__ rope_cs, int nh, int nkv,
                                                      uint16_t * __restrict__ k_cache, uint16_t * __restrict__ v_cache, int ML, float * __restrict__ qrot) {
-    constexpr int half = HD / 2, off = MODE == 0 ? 1 : half;
+    constexpr int half = HD / 2, off = rope_pair(MODE, 0, half).off;
     const int tid = threadIdx.x, blk = blockIdx.x, pos = pos_dev[0], KD = nkv * HD, QD = nh * HD;
     const bool is_q = blk < nh;
     const int g = blk - nh;
     const float * x = is_q ? qkv + blk * HD : qkv + QD + g * HD;
     if (tid < half) {
-        const int ic = MODE == 0 ? 2 * tid : tid;
+        const int ic = rope_pair(MODE, tid, half).ic;
         const float x0 = x[ic], x1 = x[ic + off], c = rope_cs[2 * tid], sn = rope_cs[2 * tid + 1];
         const float y0 = rope_rot_a(x0, x1, c, sn), y1 = rope_rot_b(x0, x1, c, sn);
         if (is_q) { qrot[blk * HD + ic] = y0; qrot[blk * HD + ic + off] = y1; }

@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
     typedef __attribute__((address_space(3))) const u32x4 * lptr4;
 
     float acc = 0.0f, accm = 0.0f;
-    float bestv = -INFINITY; int besti = 0x7fffffff;                  // EPI 2: the largest value this lane has stored and its row (first maximum wins)
+    float bestv = -INFINITY; int besti = ARGMAX_NO_INDEX;                 // EPI 2: the largest value this lane has stored and its row (first maximum wins)
     int cq = 0, cu = 0, cs = 0;                                       // consume cursor: slot ordinal, unit ordinal, slot of the unit
     while (cq < total) {
         // wait for slot cq: slots issued after it = min(iq, total) - cq - 1, three DMA instructions each
@@ -168,27 +168,18 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
                 const bool st = RPW == 8 ? j == 0 : (lane & 15) == 0;
                 if (EPI != 2 && (bias || resid)) v = gemv_bias_resid<RPW>(v, bias, resid, (size_t) unit * RPW, rowg);
                 if (st) dst[row] = v;
-                if (EPI == 2 && st && (v > bestv || (v == bestv && row < besti))) { bestv = v; besti = row; }
+                if (EPI == 2 && st) argmax_combine(bestv, besti, v, row);
             }
             acc = 0.0f; accm = 0.0f; cs = 0; cu++;
         }
     }
     if constexpr (EPI == 2) {
-        // the greedy sampler's first stage (k_argmax_partial, decode_fused.hip) on the values still in registers: (value, row) of this workgroup's largest logit, lowest row
-        // on ties, NaN never wins -- a total order, so the partition of the rows over lanes, waves and workgroups does not matter.  bias / resid carry the two output arrays.
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bestv, o, 64); const int oi = __shfl_xor(besti, o, 64);
-            if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-        }
+        // the greedy sampler's first stage (k_argmax_partial, decode_fused.hip) on the values still in registers: (value, row) of this workgroup's largest logit under
+        // the argmax_* helpers' order (common.h).  bias / resid carry the two output arrays.
+        argmax_wave(bestv, besti);
         __syncthreads();                                              // every wave has consumed its last slot and the activation row: the LDS is free
-        float * lv = (float *) lds; int * li = (int *)(lds + 64);
-        if (lane == 0) { lv[wave] = bestv; li[wave] = besti; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 16; w++) { const float ov = lv[w]; const int oi = li[w]; if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; } }
-            ((float *) bias)[blockIdx.x] = bestv; ((int *) resid)[blockIdx.x] = besti;
-        }
+        argmax_slots<16>(bestv, besti, (float *) lds, (int *)(lds + 64), lane, wave);
+        if (tid == 0) { ((float *) bias)[blockIdx.x] = bestv; ((int *) resid)[blockIdx.x] = besti; }
     }
 }
 

@@ -103,7 +103,7 @@ extern "C" int cllm_op_norm(void * stream, const cllm_tensor * src, cllm_tensor 
 
 // ================================================================================================
 // ROPE        ggml_compute_forward_rope_flt<float>, ggml-cpu/ops.cpp:5589-5865
-//   theta_i built by ITERATED fp32 multiplication (theta *= theta_scale), cos/sin per (token, pair),
+//   theta_i built by ITERATED fp32 multiplication (rope_theta, common.h), cos/sin per (token, pair),
 //   YaRN mixing (rope_yarn :5596-5611).  One workgroup per token: the first n_dims/2 threads build
 //   the cos/sin cache in LDS, then all threads rotate that token's heads.  In-place safe.
 // ================================================================================================
@@ -114,8 +114,7 @@ __global__ void __launch_bounds__(256) k_rope(tview s, tview d, const int32_t * 
     const int64_t i2 = blockIdx.x % s.ne[2], i3 = blockIdx.x / s.ne[2];
     const int half = p.n_dims / 2;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
-        float theta = (float) pos[i2];
-        for (int k = 0; k < i; k++) theta *= p.theta_scale;
+        const float theta = rope_theta(pos[i2], i, p.theta_scale);
         const float f = ff ? ff[i] : 1.0f;
         const float theta_extrap = theta / f;
         const float theta_interp = p.freq_scale * theta_extrap;
@@ -133,13 +132,13 @@ __global__ void __launch_bounds__(256) k_rope(tview s, tview d, const int32_t * 
     }
     __syncthreads();
     const int64_t ne0 = s.ne[0], nh = s.ne[1];
-    const int64_t off = p.mode == 0 ? 1 : half;
+    const int64_t off = rope_pair(p.mode, 0, half).off;
     // rotated pairs
     for (int64_t t = threadIdx.x; t < nh * half; t += blockDim.x) {
         const int64_t h = t / half; const int i = (int)(t % half);
         const float * x = (const float *)(s.data + h*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
         float *       y = (float *)(d.data + h*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
-        const int64_t ic = p.mode == 0 ? 2*i : i;
+        const int64_t ic = rope_pair(p.mode, i, half).ic;
         const float c = cache[2*i], sn = cache[2*i + 1];
         const float x0 = x[ic], x1 = x[ic + off];
         y[ic]       = rope_rot_a(x0, x1, c, sn);
@@ -192,20 +191,14 @@ __global__ void __launch_bounds__(256) k_rope_kv_store(float * __restrict__ qkv,
     extern __shared__ float cache[];                 // [hd]: cos, sin interleaved
     const int64_t tok = blockIdx.x;
     const int half = hd / 2, p = pos[tok];
-    for (int i = threadIdx.x; i < half; i += blockDim.x) {
-        float theta = (float) p;
-        for (int k = 0; k < i; k++) theta *= theta_scale;
-        float cs, sn;
-        rope_cos_sin(theta, &cs, &sn);
-        cache[2*i] = cs; cache[2*i + 1] = sn;
-    }
+    rope_table_fill(cache, p, half, theta_scale, threadIdx.x, blockDim.x);
     __syncthreads();
     const int64_t QD = (int64_t) nh * hd, KD = (int64_t) nkv * hd;
-    const int off = mode == 0 ? 1 : half;
+    const int off = rope_pair(mode, 0, half).off;
     float * q = qkv + tok * QKV;
     const float * k = q + QD, * v = k + KD;
     for (int t = threadIdx.x; t < nh * half; t += blockDim.x) {
-        const int h = t / half, i = t % half, ic = mode == 0 ? 2*i : i;
+        const int h = t / half, i = t % half, ic = rope_pair(mode, i, half).ic;
         const float c = cache[2*i], sn = cache[2*i + 1];
         float * x = q + (int64_t) h * hd;
         const float x0 = x[ic], x1 = x[ic + off];
@@ -214,7 +207,7 @@ __global__ void __launch_bounds__(256) k_rope_kv_store(float * __restrict__ qkv,
     if (p < 0 || p >= ML) return;                    // (the CPU asserts; never write out of bounds)
     uint16_t * kr = k_cache + (int64_t) p * KD;
     for (int t = threadIdx.x; t < nkv * half; t += blockDim.x) {
-        const int h = t / half, i = t % half, ic = mode == 0 ? 2*i : i;
+        const int h = t / half, i = t % half, ic = rope_pair(mode, i, half).ic;
         const float c = cache[2*i], sn = cache[2*i + 1];
         const float * x = k + (int64_t) h * hd;
         const float x0 = x[ic], x1 = x[ic + off];
@@ -271,8 +264,7 @@ __global__ void __launch_bounds__(256) k_soft_max(tview s, tview d, const char *
         float e[8];
 #pragma unroll
         for (int l = 0; l < 8; l++) { e[l] = ggml_expf_poly(val(g + l) - mx); y[g + l] = e[l]; }
-        const float a0 = e[0] + e[4], a1 = e[1] + e[5], a2 = e[2] + e[6], a3 = e[3] + e[7];
-        sum += (double)((a0 + a2) + (a1 + a3));
+        sum += (double) soft_group8_sum(e);
     }
     if (lane == 0) for (int64_t i = nv; i < n; i++) { const float e = libm_expf(val(i) - mx); y[i] = e; sum += (double) e; }
     sum = wave_sum_d(sum);
@@ -327,8 +319,7 @@ __global__ void __launch_bounds__(256) k_soft_max_causal_reg(tview s, tview d, f
         if (g0 < n_vis) {
 #pragma unroll
             for (int l = 0; l < 8; l++) e[t][l] = ggml_expf_poly(e[t][l] - mx);
-            const float a0 = e[t][0] + e[t][4], a1 = e[t][1] + e[t][5], a2 = e[t][2] + e[t][6], a3 = e[t][3] + e[t][7];
-            sum += (double)((a0 + a2) + (a1 + a3));
+            sum += (double) soft_group8_sum(e[t]);
         }
     }
     sum = wave_sum_d(sum);
@@ -393,16 +384,11 @@ __global__ void __launch_bounds__(256) k_soft_max_causal_lds(tview s, tview d, f
         float e[8];
 #pragma unroll
         for (int l = 0; l < 8; l++) { e[l] = ggml_expf_poly(sm[g0 + l] - mx); sm[g0 + l] = e[l]; }
-        const float a0 = e[0] + e[4], a1 = e[1] + e[5], a2 = e[2] + e[6], a3 = e[3] + e[7];
-        gsum[g0 >> 3] = (a0 + a2) + (a1 + a3);
+        gsum[g0 >> 3] = soft_group8_sum(e);
     }
     __syncthreads();
-    if (wave == 0) {
-        double sum = 0.0;
-        for (int gq = lane; gq < (nv_vis >> 3); gq += 64) sum += (double) gsum[gq];
-        sum = wave_sum_d(sum);
-        double rinv = 1.0 / sum;                                      // (ORDER: soft_total_order_safe, common.h; groups beyond nv_vis are exact zeros in the reference's sum)
-        if (__builtin_expect(!soft_total_order_safe(rinv, n >> 3), 0)) rinv = 1.0 / soft_sum_serial_groups(gsum, nv_vis >> 3, sm, 0, 0);
+    if (wave == 0) {                                                  // (no leftovers: n % 8 == 0; groups beyond nv_vis are exact zeros in the reference's sum of n / 8 terms)
+        const double rinv = soft_total_rinv_groups(gsum, nv_vis >> 3, sm, 0, 0, mx, n >> 3, lane);
         if (lane == 0) red_d[0] = rinv;
     }
     __syncthreads();

@@ -25,12 +25,6 @@ __device__ __forceinline__ int lane_xor4_i(int v) {
     const int r = __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHL4, 0xf, 0x5, false);      // lanes 0-3, 8-11 of a row <- lane + 4
     return __builtin_amdgcn_update_dpp(r, v, DPP_ROW_SHR4, 0xf, 0xA, false);             // lanes 4-7, 12-15        <- lane - 4
 }
-// compiler-level ordering of the wave's own LDS records (the LDS executes one wave's DS operations in order)
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- chain records: per wave, 8 pairs of super-blocks x 12 slots x {x_i, d_i, x_i+1, d_i+1} floats (+ 64 B so that the idle lanes
 //      12..15 of a row read inside the buffer) ----

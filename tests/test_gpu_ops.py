@@ -1276,3 +1276,71 @@ def test_fuzz_parity_thirty_seconds(gpu):
     tail = (r.stdout + r.stderr)[-1500:]
     assert r.returncode == 0, tail
     assert "0 mismatches" in r.stdout or "mismatches: 0" in r.stdout or "0 mismatch" in r.stdout, tail
+
+
+# ---- the greedy sampler's two-launch ops (argmax_* helpers, common.h): first maximum, NaN never wins, nothing to pick -> id 0 ----
+def argmax_inputs(n):
+    """(name, logits, expected id) for one n.  k_argmax_partial cuts [0, n) into 256 slices of per = ceil(n / 256) values (n 1, 255: empty slices; 256: one value each;
+    257: per 2, half the slices empty and the last one short; 65537: per 257, each wave of a slice takes several values and the last slice holds 2)."""
+    per = -(-n // 256)
+    g = np.random.default_rng(1000 + n)
+    base = g.standard_normal(n).astype(np.float32)
+    top = np.float32(9.0)
+    out = []
+    lo = (-(-n // per) // 2) * per                  # first value of a slice in the middle of the non-empty ones (not id 0, which is also what an empty reduce gives)
+    pairs = {"inside_one_slice": (lo, min(lo + per - 1, n - 1)), "across_two_slices": (min(lo + per - 1, n - 1), min(lo + per, n - 1)), "first_and_last": (0, n - 1),
+             "last_slice_twice": (max(0, n - 2), n - 1)}
+    for name, (a, b) in pairs.items():
+        x = base.copy(); x[a] = x[b] = top
+        out.append((f"maximum_twice_{name}", x, min(a, b)))
+    out.append(("all_minus_inf", np.full(n, -np.inf, np.float32), 0))
+    x = base.copy()
+    m = n // 2
+    x[m] = top
+    for i in (0, m - 1, m + 1, n - 1):
+        if 0 <= i < n and i != m:
+            x[i] = np.nan
+    out.append(("nans_around_the_maximum", x, m))
+    x = base.copy(); x[n - 1] = np.inf; x[n // 3] = np.inf; x[0] = top
+    out.append(("plus_inf", x, n // 3))
+    for name, x, want in out:                       # numpy's first maximum (NaNs skipped), except where every value is -inf: the kernels state id 0
+        assert want == (0 if name == "all_minus_inf" else int(np.nanargmax(x))), (name, n)
+    return out
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 65537])
+def test_argmax_advance_and_set_pick_the_first_maximum(gpu, n):
+    """cllm_op_argmax_advance and cllm_op_argmax_set against numpy's first maximum, with their side effects: tok_host written when given (and not needed),
+    every increment pointer advanced by exactly 1, exactly n_set of the table's records stored"""
+    L, T = gpu.lib.get(), gpu.Tensor
+    scratch = gpu.tensor.Buffer(4096)
+    host = C.c_void_p()
+    gpu.lib.check(L.cllm_host_malloc(C.byref(host), 64), "host_malloc")
+    try:
+        tok_host = C.c_int32.from_address(host.value)
+        for name, x, want in argmax_inputs(n):
+            logits = T.from_numpy(x)
+            for with_host in (True, False):
+                # advance: three counters to increment, a fourth word that is nobody's
+                tok = T.from_numpy(np.array([-7], np.int32))
+                cnt = T.from_numpy(np.array([5, -1, 100, 77], np.int32))
+                ptrs = T.from_numpy(np.array([cnt.data_ptr().value + 4 * i for i in range(3)], np.uint64).view(np.int64))
+                tok_host.value = -7
+                gpu.lib.check(L.cllm_op_argmax_advance(None, logits.data_ptr(), n, tok.data_ptr(), host if with_host else None, ptrs.data_ptr(), 3, scratch.ptr), "argmax_advance")
+                assert int(tok.numpy()[0]) == want, (name, n, "advance", int(tok.numpy()[0]), want)
+                assert cnt.numpy().tolist() == [6, 0, 101, 77], (name, n, cnt.numpy())
+                assert tok_host.value == (want if with_host else -7), (name, n, "tok_host", tok_host.value)
+                # set: a table of five records, three of them handed over
+                tok = T.from_numpy(np.array([-7], np.int32))
+                tgt = T.from_numpy(np.array([1, 2, 3, 4, 5], np.int32))
+                recs = np.zeros(5, np.dtype([("ptr", np.uint64), ("val", np.int32), ("pad", np.int32)]))
+                recs["ptr"] = [tgt.data_ptr().value + 4 * i for i in range(5)]
+                recs["val"] = [41, -42, 43, 44, 45]
+                table = T.from_numpy(recs.view(np.uint8).view(np.int32))
+                tok_host.value = -7
+                gpu.lib.check(L.cllm_op_argmax_set(None, logits.data_ptr(), n, tok.data_ptr(), host if with_host else None, table.data_ptr(), 3, scratch.ptr), "argmax_set")
+                assert int(tok.numpy()[0]) == want, (name, n, "set", int(tok.numpy()[0]), want)
+                assert tgt.numpy().tolist() == [41, -42, 43, 4, 5], (name, n, tgt.numpy())
+                assert tok_host.value == (want if with_host else -7), (name, n, "tok_host", tok_host.value)
+    finally:
+        L.cllm_host_free(host)

@@ -78,6 +78,34 @@ def test_cos_sin_of_the_device_swept_through_the_op(gpu, case):
         [(float(angles[i]).hex(), got.reshape(-1, 2)[i].tolist(), want.reshape(-1, 2)[i].tolist()) for i in bad[:6]])
 
 
+TABLE_POSITIONS = [0, 1, 4095, 131071]
+
+
+@pytest.mark.parametrize("mode", [0, 2], ids=["normal", "neox"])
+@pytest.mark.parametrize("head_dim", [2, 64, 128, 192])
+def test_rope_table_has_the_words_of_rope(gpu, head_dim, mode):
+    """cllm_op_rope_table against cllm_op_rope, word for word: both take the plain table entry (rope_theta, rope_entry, common.h) and must not drift apart.
+    Rows whose pairs are (1, 0), n_dims == head_dim, no frequency factors, freq_scale 1, ext_factor 0, attn_factor 1: rope_rot_a / rope_rot_b return exactly
+    (cos, sin), so token t of the rotated tensor is the table of position TABLE_POSITIONS[t] -- interleaved as the table is in mode 0, cos | sin halves in mode 2.
+    What each case reaches: head_dim 2 -- pair 0 alone, the recurrence of zero multiplications; 64 -- 32 pairs, half of the table kernel's 64 threads idle;
+    128 -- one full trip of the 64-thread fill; 192 -- 96 pairs, the fill's second trip (threads 0..31 only) and recurrences of up to 95 multiplications;
+    mode 0 / 2 -- both arms of rope_pair in k_rope; position 0 -- theta == 0 for every pair (cos 1, sin +0); 1 -- angles of at most 1; 4095 and 131071 -- large angles
+    (pair 0: theta == pos) shrinking through every quadrant down the table, so the recurrence's rounding shows in cos and sin."""
+    half = head_dim // 2
+    x = np.zeros((len(TABLE_POSITIONS), 1, head_dim), np.float32)
+    x[..., (slice(0, None, 2) if mode == 0 else slice(0, half))] = 1.0
+    pos = np.array(TABLE_POSITIONS, np.int32)
+    rot = gpu.ops.rope_ext(gpu.Tensor.from_numpy(x), gpu.Tensor.from_numpy(pos), None, head_dim, mode, freq_base=10000.0).numpy().reshape(len(TABLE_POSITIONS), head_dim)
+    for t, p in enumerate(TABLE_POSITIONS):
+        cs = gpu.Tensor.from_numpy(np.full(head_dim, 7.0, np.float32))
+        gpu.lib.check(gpu.lib.get().cllm_op_rope_table(None, gpu.Tensor.from_numpy(pos[t:t + 1]).data_ptr(), head_dim, 10000.0, cs.data_ptr()), "rope_table")
+        table = cs.numpy().reshape(half, 2)
+        want = rot[t].reshape(half, 2) if mode == 0 else np.stack([rot[t, :half], rot[t, half:]], axis=1)
+        E.assert_same_words(table, np.ascontiguousarray(want), None, f"rope_table head_dim {head_dim} mode {mode} position {p}")
+        if p == 0:
+            assert np.array_equal(table.view(np.uint32), np.tile(np.array([1.0, 0.0], np.float32).view(np.uint32), (half, 1)))
+
+
 # ---- what is declined ----------------------------------------------------------------------------------------------------------------------
 def declined(gpu, rc, word, ne=(64, 2, 5), nb=None, pos_len=5, **kw):
     x = np.arange(2 * 5 * 2 * 64, dtype=np.float32)
