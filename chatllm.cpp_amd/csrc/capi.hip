@@ -42,28 +42,8 @@ extern "C" const char * cllm_option_str(const char * name) { const int id = opti
 extern "C" size_t cllm_options_describe(char * buf, size_t size) { return opt_describe(buf, size); }
 
 // ---- type traits (ggml.c type_traits[]) -------------------------------------------------------------------
-extern "C" size_t cllm_type_size(int type) {
-    switch (type) {
-        case CLLM_TYPE_F32: case CLLM_TYPE_I32: return 4;
-        case CLLM_TYPE_F16: return 2;
-        case CLLM_TYPE_I64: return 8;
-        case CLLM_TYPE_Q4_0: return 18; case CLLM_TYPE_Q4_1: return 20; case CLLM_TYPE_Q8_0: return 34; case CLLM_TYPE_Q4_K: return 144;
-        case CLLM_TYPE_Q5_K: return 176; case CLLM_TYPE_Q6_K: return 210;
-        case CLLM_TYPE_Q5_0: return 22; case CLLM_TYPE_Q5_1: return 24; case CLLM_TYPE_IQ4_NL: return 18; case CLLM_TYPE_MXFP4: return 17;
-        case CLLM_TYPE_Q2_K: return 84; case CLLM_TYPE_Q3_K: return 110; case CLLM_TYPE_IQ4_XS: return 136; case CLLM_TYPE_TQ1_0: return 54; case CLLM_TYPE_TQ2_0: return 66;
-        case CLLM_TYPE_IQ2_XXS: return 66; case CLLM_TYPE_IQ2_XS: return 74; case CLLM_TYPE_IQ2_S: return 82; case CLLM_TYPE_IQ3_XXS: return 98; case CLLM_TYPE_IQ3_S: return 110; case CLLM_TYPE_IQ1_S: return 50; case CLLM_TYPE_IQ1_M: return 56;
-    }
-    return 0;
-}
-extern "C" int cllm_blck_size(int type) {
-    switch (type) {
-        case CLLM_TYPE_F32: case CLLM_TYPE_I32: case CLLM_TYPE_F16: case CLLM_TYPE_I64: return 1;
-        case CLLM_TYPE_Q4_0: case CLLM_TYPE_Q4_1: case CLLM_TYPE_Q8_0: case CLLM_TYPE_Q5_0: case CLLM_TYPE_Q5_1: case CLLM_TYPE_IQ4_NL: case CLLM_TYPE_MXFP4: return 32;
-        case CLLM_TYPE_Q4_K: case CLLM_TYPE_Q5_K: case CLLM_TYPE_Q6_K: case CLLM_TYPE_Q2_K: case CLLM_TYPE_Q3_K: case CLLM_TYPE_IQ4_XS: case CLLM_TYPE_TQ1_0: case CLLM_TYPE_TQ2_0:
-        case CLLM_TYPE_IQ2_XXS: case CLLM_TYPE_IQ2_XS: case CLLM_TYPE_IQ2_S: case CLLM_TYPE_IQ3_XXS: case CLLM_TYPE_IQ3_S: case CLLM_TYPE_IQ1_S: case CLLM_TYPE_IQ1_M: return 256;
-    }
-    return 0;
-}
+extern "C" size_t cllm_type_size(int type) { return wtype_size(type); }        // the table: types.def
+extern "C" int cllm_blck_size(int type) { return wtype_blck(type); }
 extern "C" size_t cllm_row_size(int type, int64_t ne) {
     const int bs = cllm_blck_size(type);
     return bs ? cllm_type_size(type) * (size_t)(ne / bs) : 0;
@@ -303,6 +283,19 @@ extern "C" size_t cllm_mul_mat_wsize(const cllm_tensor * src0, const cllm_tensor
     return act_row_bytes(src1->ne[0], act_kind(src0->type)) * (size_t) t_nrows(src1);
 }
 
+// ---- operand predicates of the quantized mat-mul entry points ----
+// data and nb[1..3] of a weight tensor as its type's kernels load them (types.def: row_align)
+static bool rows_aligned(const cllm_tensor * t, int nd = 3) {
+    uintptr_t v = (uintptr_t) t->data;
+    for (int i = 1; i <= nd; i++) v |= (uintptr_t) t->nb[i];
+    return v % (uintptr_t) wtype_row_align(t->type) == 0;
+}
+// rows of a tuned type back to back / a 2-D matrix of such rows: what the single-launch decode forms take
+static bool dense_quant_rows(const cllm_tensor * t) { return is_quant_type(t->type) && t->nb[1] == cllm_row_size(t->type, t->ne[0]); }
+static bool dense_quant_matrix(const cllm_tensor * t) { return dense_quant_rows(t) && t->ne[2] == 1 && t->ne[3] == 1; }
+// 16-byte aligned vectors (the decode forms read whole 16-byte pieces)
+template <class... P> static bool aligned16(P... p) { return ((... | (uintptr_t) p) & 15) == 0; }
+
 static int check_mm(const cllm_tensor * src0, const cllm_tensor * src1, const cllm_tensor * dst, const char * name) {
     if (!src0 || !src1 || !dst) FAIL(CLLM_E_INVALID, "%s: null tensor", name);
     if (src1->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "%s: src1/dst must be F32", name);
@@ -310,7 +303,58 @@ static int check_mm(const cllm_tensor * src0, const cllm_tensor * src1, const cl
     if (src0->ne[0] != src1->ne[0]) FAIL(CLLM_E_INVALID, "%s: K mismatch %lld vs %lld", name, (long long) src0->ne[0], (long long) src1->ne[0]);
     if (src0->nb[0] != cllm_type_size(src0->type) || src1->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "%s: rows must be dense", name);
     if (src0->ne[0] % cllm_blck_size(src0->type)) FAIL(CLLM_E_INVALID, "%s: K not a multiple of the block size", name);
-    if (src0->type == CLLM_TYPE_Q4_1 && ((uintptr_t) src0->data % 4 || src0->nb[1] % 4 || src0->nb[2] % 4 || src0->nb[3] % 4)) FAIL(CLLM_E_UNSUPPORTED, "%s: Q4_1 rows must be 4-byte aligned", name);
+    if (src0->type == CLLM_TYPE_Q4_1 && !rows_aligned(src0)) FAIL(CLLM_E_UNSUPPORTED, "%s: Q4_1 rows must be %d-byte aligned", name, wtype_row_align(src0->type));
+    return CLLM_OK;
+}
+
+// ---- the route: which launchers a quantized product tries, in order (each declines with CLLM_E_UNSUPPORTED).  ONE statement: the op, its fused form and the bench helper walk it.
+enum mm_kernel { MM_DENSE_F16, MM_MMQ, MM_MMX, MM_MMVQ };
+struct mm_route_t { int n; mm_kernel k[3]; };
+static mm_route_t mm_route(int64_t M, int64_t nrows) {
+    switch (gemm_path(M, nrows)) {
+        case 2:  return prefill_f16_enabled() ? mm_route_t{ 3, { MM_DENSE_F16, MM_MMQ, MM_MMVQ } }      // opt-in: dequantize -> dense fp16 GEMM; a different computation than the reference's
+                                              : mm_route_t{ 2, { MM_MMQ, MM_MMVQ } };
+        case 1:  return mm_route_t{ 2, { MM_MMX, MM_MMVQ } };                                             // the reference's order on the matrix cores
+        default: return mm_route_t{ 1, { MM_MMVQ } };
+    }
+}
+// fused_only (cllm_op_mul_mat_ex): the kernels with a prologue / epilogue form -- mmx or mmq, no dense GEMM, no mat-vec fallback
+static int mm_walk(hipStream_t st, const mm_route_t & r, bool fused_only, int wtype, const tview & w, const void * act, size_t stride, const tview & x, const tview & d,
+                   const float * resid = nullptr, int64_t ldr = 0, int epi = 0) {
+    int rc = CLLM_E_UNSUPPORTED;
+    for (int i = 0; i < r.n && rc == CLLM_E_UNSUPPORTED; i++) switch (r.k[i]) {
+        case MM_DENSE_F16: if (!fused_only) rc = launch_dense_f16(st, wtype, w, x, d); break;
+        case MM_MMQ:       rc = launch_mmq(st, wtype, w, act, stride, x, d, resid, ldr, epi); break;
+        case MM_MMX:       rc = launch_mmx(st, wtype, w, act, stride, x, d, resid, ldr, epi); break;
+        case MM_MMVQ:      if (!fused_only) rc = launch_mmvq(st, wtype, w, act, stride, x.ne[1], x, d); break;
+    }
+    return rc;
+}
+
+// wdata holds the act rows of src1; the operands as the kernels load them (in front of both halves of cllm_op_mul_mat)
+static int mm_wdata_and_alignment(const cllm_tensor * src0, const cllm_tensor * src1, const void * wdata, size_t wsize, size_t stride) {
+    const size_t need = stride * (size_t) t_nrows(src1);
+    if (!wdata || wsize < need) FAIL(CLLM_E_INVALID, "mul_mat: wdata too small (%zu < %zu)", wsize, need);
+    if ((uintptr_t) wdata % 16 || (is_quant_type(src0->type) && (uintptr_t) src0->data % 2) || (uintptr_t) src1->data % 16 || src1->nb[1] % 16 || src1->nb[2] % 16 || src1->nb[3] % 16)
+        FAIL(CLLM_E_UNSUPPORTED, "mul_mat: operand alignment");
+    if (src0->type == CLLM_TYPE_Q4_K && !rows_aligned(src0)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat: Q4_K rows must be %d-byte aligned", wtype_row_align(src0->type));
+    return CLLM_OK;
+}
+// fn(w, act, x, d) for every (i12, i13) slice of the broadcast product: the 2-D weight matrix, its act rows, the slice of src1 and of dst
+template <class Fn>
+static int for_each_mat_slice(const cllm_tensor * src0, const cllm_tensor * src1, const cllm_tensor * dst, const void * wdata, size_t stride, Fn && fn) {
+    const int64_t r2 = src1->ne[2] / src0->ne[2], r3 = src1->ne[3] / src0->ne[3];
+    for (int64_t i13 = 0; i13 < src1->ne[3]; i13++)
+    for (int64_t i12 = 0; i12 < src1->ne[2]; i12++) {
+        tview w = tv(src0), x = tv(src1), d = tv(dst);
+        w.data += (i12 / r2) * w.nb[2] + (i13 / r3) * w.nb[3];
+        w.ne[2] = w.ne[3] = 1;
+        x.data += i12 * x.nb[2] + i13 * x.nb[3];
+        d.data += i12 * d.nb[2] + i13 * d.nb[3];
+        const char * act = (const char *) wdata + (size_t)(i12 * src1->ne[1] + i13 * src1->ne[1] * src1->ne[2]) * stride;
+        const int rc = fn(w, act, x, d);
+        if (rc) return rc;
+    }
     return CLLM_OK;
 }
 
@@ -324,70 +368,27 @@ extern "C" int cllm_op_mul_mat(void * stream, const cllm_tensor * src0, const cl
     if (src0->ne[0] == 0) return cllm_memset(dst->data, 0, dst->nb[3] * (size_t) dst->ne[3], stream);
 
     if (!is_quant(src0->type)) return launch_mul_mat_f(st, src0->type, tv(src0), tv(src1), tv(dst));
-    if (is_kq_type(src0->type)) {                      // the coverage types: the exact-order kernel for any number of columns (gemv_kq.hip)
-        const size_t stride = act_row_bytes(src0->ne[0], act_kind(src0->type)), need = stride * (size_t) t_nrows(src1);
-        if (!wdata || wsize < need) FAIL(CLLM_E_INVALID, "mul_mat: wdata too small (%zu < %zu)", wsize, need);
-        if ((uintptr_t) wdata % 16 || (uintptr_t) src1->data % 16 || src1->nb[1] % 16 || src1->nb[2] % 16 || src1->nb[3] % 16) FAIL(CLLM_E_UNSUPPORTED, "mul_mat: operand alignment");
-        if ((rc = launch_quantize_act(st, act_kind(src0->type), tv(src1), wdata, stride))) return rc;
-        const int64_t r2 = src1->ne[2] / src0->ne[2], r3 = src1->ne[3] / src0->ne[3];
-        for (int64_t i13 = 0; i13 < src1->ne[3]; i13++)
-        for (int64_t i12 = 0; i12 < src1->ne[2]; i12++) {
-            tview w = tv(src0);
-            w.data += (i12 / r2) * w.nb[2] + (i13 / r3) * w.nb[3];
-            const char * act = (const char *) wdata + (size_t)(i12 * src1->ne[1] + i13 * src1->ne[1] * src1->ne[2]) * stride;
-            if (dst->nb[1] % 4) FAIL(CLLM_E_INVALID, "mul_mat: dst stride");
-            rc = launch_gemv_kq(st, src0->type, w, act, stride, src1->ne[1], (float *)((char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]), (int64_t)(dst->nb[1] / 4));
-            if (rc == CLLM_E_UNSUPPORTED) FAIL(rc, "mul_mat: type %d: shape or alignment not taken", src0->type);
-            if (rc) return rc;
-        }
-        return CLLM_OK;
-    }
-
     const int kind = act_kind(src0->type);
     const int64_t K = src0->ne[0];
     const size_t stride = act_row_bytes(K, kind);
-    const size_t need = stride * (size_t) t_nrows(src1);
-    if (!wdata || wsize < need) FAIL(CLLM_E_INVALID, "mul_mat: wdata too small (%zu < %zu)", wsize, need);
-    if ((uintptr_t) wdata % 16 || (uintptr_t) src0->data % 2 || (uintptr_t) src1->data % 16 || src1->nb[1] % 16 || src1->nb[2] % 16 || src1->nb[3] % 16)
-        FAIL(CLLM_E_UNSUPPORTED, "mul_mat: operand alignment");
-    if (src0->type == CLLM_TYPE_Q4_K && ((uintptr_t) src0->data % 16 || src0->nb[1] % 16 || src0->nb[2] % 16 || src0->nb[3] % 16))
-        FAIL(CLLM_E_UNSUPPORTED, "mul_mat: Q4_K rows must be 16-byte aligned");
+    if ((rc = mm_wdata_and_alignment(src0, src1, wdata, wsize, stride))) return rc;
     // a single dense activation column (decode): quantize it inside the mat-vec (one launch instead of two; the decode kernels)
-    if (src1->ne[1] == 1 && src1->ne[2] == 1 && src1->ne[3] == 1 && src0->ne[2] == 1 && src0->ne[3] == 1 && src1->nb[0] == 4 && dst->nb[0] == 4 &&
-        src0->nb[1] == cllm_row_size(src0->type, K) && K % act_blk(kind) == 0 && act_row_bytes(K, kind) <= 160 * 1024) {
+    if (dense_quant_matrix(src0) && src1->ne[1] == 1 && src1->ne[2] == 1 && src1->ne[3] == 1 && src1->nb[0] == 4 && dst->nb[0] == 4 && K % act_blk(kind) == 0 && stride <= 160 * 1024) {
         rc = launch_gemv_decode(st, src0->type, src0->data, K, src0->ne[1], 2, (const float *) src1->data, nullptr, 0.0f, 0, (float *) dst->data, nullptr, nullptr);
         if (rc != CLLM_E_UNSUPPORTED) return rc;          // very long rows: the two-launch path below
     }
-
-    rc = launch_quantize_act(st, kind, tv(src1), wdata, stride);
-    if (rc) return rc;
-
-    const int64_t r2 = src1->ne[2] / src0->ne[2], r3 = src1->ne[3] / src0->ne[3];
-    const tview x = tv(src1);
-    for (int64_t i13 = 0; i13 < src1->ne[3]; i13++)
-    for (int64_t i12 = 0; i12 < src1->ne[2]; i12++) {
-        tview w = tv(src0);
-        w.data += (i12 / r2) * w.nb[2] + (i13 / r3) * w.nb[3];
-        w.ne[2] = w.ne[3] = 1;
-        tview d = tv(dst);
-        d.data += i12 * d.nb[2] + i13 * d.nb[3];
-        const char * act = (const char *) wdata + (size_t)(i12 * src1->ne[1] + i13 * src1->ne[1] * src1->ne[2]) * stride;
-        const int path = gemm_path(src1->ne[1], src0->ne[1]);
-        if (path) {
-            rc = CLLM_E_UNSUPPORTED;
-            if (path == 2 && prefill_f16_enabled()) {            // opt-in: dequantize -> dense fp16 GEMM (dense_f16.hip); a different computation than the reference's
-                tview x1 = x; x1.data += i12 * x.nb[2] + i13 * x.nb[3];
-                rc = launch_dense_f16(st, src0->type, w, x1, d);
-            }
-            if (rc == CLLM_E_UNSUPPORTED && path == 1) rc = launch_mmx(st, src0->type, w, act, stride, x, d);      // the reference's order on the matrix cores
-            if (rc == CLLM_E_UNSUPPORTED && path == 2) rc = launch_mmq(st, src0->type, w, act, stride, x, d);
-            if (rc == CLLM_E_UNSUPPORTED) rc = launch_mmvq(st, src0->type, w, act, stride, src1->ne[1], x, d);
-        } else {
-            rc = launch_mmvq(st, src0->type, w, act, stride, src1->ne[1], x, d);
-        }
-        if (rc) return rc;
-    }
-    return CLLM_OK;
+    if ((rc = launch_quantize_act(st, kind, tv(src1), wdata, stride))) return rc;
+    if (is_kq_type(src0->type))                        // the coverage types: the exact-order kernel for any number of columns (gemv_kq.hip)
+        return for_each_mat_slice(src0, src1, dst, wdata, stride, [&](const tview & w, const char * act, const tview &, const tview & d) -> int {
+            if (d.nb[1] % 4) FAIL(CLLM_E_INVALID, "mul_mat: dst stride");
+            const int r = launch_gemv_kq(st, src0->type, w, act, stride, src1->ne[1], (float *) d.data, (int64_t)(d.nb[1] / 4));
+            if (r == CLLM_E_UNSUPPORTED) FAIL(r, "mul_mat: type %d: shape or alignment not taken", src0->type);
+            return r;
+        });
+    const mm_route_t route = mm_route(src1->ne[1], src0->ne[1]);
+    return for_each_mat_slice(src0, src1, dst, wdata, stride, [&](const tview & w, const char * act, const tview & x, const tview & d) -> int {
+        return mm_walk(st, route, false, src0->type, w, act, stride, x, d);
+    });
 }
 
 int mmq_min_cols_get() { return mmq_min_cols(); }
@@ -411,8 +412,7 @@ extern "C" int cllm_op_mul_mat_ex(void * stream, const cllm_tensor * src0, const
     const size_t stride = act_row_bytes(K, kind), need = stride * (size_t) M;
     if (!wdata || wsize < need) FAIL(CLLM_E_INVALID, "mul_mat_ex: wdata too small (%zu < %zu)", wsize, need);
     if ((uintptr_t) wdata % 16 || (uintptr_t) src0->data % 2 || (pro != 5 && ((uintptr_t) src1->data % 16 || src1->nb[1] % 16))) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_ex: operand alignment");
-    if (src0->type == CLLM_TYPE_Q4_K && ((uintptr_t) src0->data % 16 || src0->nb[1] % 16)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_ex: Q4_K rows must be 16-byte aligned");
-    if (src0->type == CLLM_TYPE_Q4_1 && ((uintptr_t) src0->data % 4 || src0->nb[1] % 4)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_ex: Q4_1 rows must be 4-byte aligned");
+    if (wtype_row_align(src0->type) > 2 && !rows_aligned(src0, 1)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_ex: these rows must be %d-byte aligned", wtype_row_align(src0->type));      // (2: the data pointer, above)
     hipStream_t st = (hipStream_t) stream;
     int rc = pro == 3 ? launch_quantize_act_silu(st, kind, tv(src1), wdata, stride)
            : pro == 1 ? launch_quantize_act_norm(st, kind, tv(src1), (const float *) norm_w->data, eps, wdata, stride)
@@ -422,10 +422,29 @@ extern "C" int cllm_op_mul_mat_ex(void * stream, const cllm_tensor * src0, const
     if (rc == CLLM_E_UNSUPPORTED) FAIL(rc, "mul_mat_ex: this prologue takes 16-byte aligned rows (norm: of at most 16384 values)");
     if (rc) return rc;
     tview x = tv(src1); if (pro == 3) x.ne[0] = K;
-    rc = gemm_path(M, src0->ne[1]) != 2 ? launch_mmx(st, src0->type, tv(src0), wdata, stride, x, tv(dst), resid ? (const float *) resid->data : nullptr, resid ? (int64_t)(resid->nb[1] / 4) : 0, epi)
-                             : launch_mmq(st, src0->type, tv(src0), wdata, stride, x, tv(dst), resid ? (const float *) resid->data : nullptr, resid ? (int64_t)(resid->nb[1] / 4) : 0, epi);
+    // the route's fused forms only: mmx, or mmq in the fast mode (M >= exact_gemm_min_cols(0) above: never the mat-vec's columns)
+    rc = mm_walk(st, mm_route(M, src0->ne[1]), true, src0->type, tv(src0), wdata, stride, x, tv(dst), resid ? (const float *) resid->data : nullptr, resid ? (int64_t)(resid->nb[1] / 4) : 0, epi);
     if (rc == CLLM_E_UNSUPPORTED) FAIL(rc, "mul_mat_ex: the matrix-core kernel does not take this shape");
     return rc;
+}
+
+// ---- the measurement helpers' timer: `warm` untimed calls of body(i) (they also page in code objects), then `iters` timed ones between two events; *avg_us = elapsed / iters.
+// The events live in a holder, so every return path destroys them.
+struct event_pair { hipEvent_t e0 = nullptr, e1 = nullptr; ~event_pair() { if (e0) (void) hipEventDestroy(e0); if (e1) (void) hipEventDestroy(e1); } };
+template <class Body>
+static int timed_launches(hipStream_t st, int warm, int iters, Body && body, float * avg_us) {
+    event_pair ev;
+    HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1));
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1) HIP_TRY(hipEventRecord(ev.e0, st));
+        for (int i = 0; i < (pass == 0 ? warm : iters); i++) { const int rc = body(i); if (rc) return rc; }
+    }
+    HIP_TRY(hipEventRecord(ev.e1, st));
+    HIP_TRY(hipEventSynchronize(ev.e1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *avg_us = ms * 1e3f / (float) iters;
+    return CLLM_OK;
 }
 
 extern "C" int cllm_bench_mul_mat_kernel(void * stream, const cllm_tensor * src0, void * const * src0_datas, int n_src0, const cllm_tensor * src1,
@@ -440,27 +459,11 @@ extern "C" int cllm_bench_mul_mat_kernel(void * stream, const cllm_tensor * src0
     if (!wdata || wsize < stride * (size_t) src1->ne[1]) FAIL(CLLM_E_INVALID, "bench_mul_mat_kernel: wdata too small");
     rc = launch_quantize_act(st, kind, tv(src1), wdata, stride);
     if (rc) return rc;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    const int path = gemm_path(src1->ne[1], src0->ne[1]);
-    for (int pass = 0; pass < 2; pass++) {             // pass 0 = warm-up (also pages in code objects), pass 1 = timed
-        if (pass == 1) HIP_TRY(hipEventRecord(e0, st));
-        const int n = pass == 0 ? (n_src0 < 4 ? n_src0 : 4) : iters;
-        for (int i = 0; i < n; i++) {
-            tview w = tv(src0); w.data = (char *) src0_datas[i % n_src0];
-            rc = !path ? CLLM_E_UNSUPPORTED : (path == 2 && prefill_f16_enabled()) ? launch_dense_f16(st, src0->type, w, tv(src1), tv(dst))
-                                            : path == 1 ? launch_mmx(st, src0->type, w, wdata, stride, tv(src1), tv(dst)) : launch_mmq(st, src0->type, w, wdata, stride, tv(src1), tv(dst));
-            if (rc == CLLM_E_UNSUPPORTED) rc = launch_mmvq(st, src0->type, w, wdata, stride, src1->ne[1], tv(src1), tv(dst));
-            if (rc) return rc;
-        }
-    }
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-    *avg_us = ms * 1e3f / (float) iters;
-    return CLLM_OK;
+    const mm_route_t route = mm_route(src1->ne[1], src0->ne[1]);      // what cllm_op_mul_mat launches for these operands, fallbacks included
+    return timed_launches(st, n_src0 < 4 ? n_src0 : 4, iters, [&](int i) -> int {
+        tview w = tv(src0); w.data = (char *) src0_datas[i % n_src0];
+        return mm_walk(st, route, false, src0->type, w, wdata, stride, tv(src1), tv(dst));
+    }, avg_us);
 }
 
 // One launch for a node pattern around a single-column quantized MUL_MAT (what a ggml backend's graph_compute can fuse):
@@ -471,8 +474,8 @@ extern "C" int cllm_bench_mul_mat_kernel(void * stream, const cllm_tensor * src0
 extern "C" int cllm_op_mul_mat_vec_fused(void * stream, const cllm_tensor * src0, int pro, const float * px, const float * pw, float eps, int epi,
                                          const float * resid, float * dst) {
     if (!src0 || !px || !dst || (pro != 1 && pro != 2 && pro != 4) || ((pro == 1 || pro == 4) && !pw) || (epi != 0 && epi != 1)) FAIL(CLLM_E_INVALID, "mul_mat_vec_fused: arguments");
-    if (!is_quant_type(src0->type) || src0->ne[2] != 1 || src0->ne[3] != 1 || src0->nb[1] != cllm_row_size(src0->type, src0->ne[0])) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_vec_fused: src0 must be a dense 2-D quantized matrix");
-    if (((uintptr_t) px | (uintptr_t) pw | (uintptr_t) src0->data) & 15) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_vec_fused: alignment");
+    if (!dense_quant_matrix(src0)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_vec_fused: src0 must be a dense 2-D quantized matrix");
+    if (!aligned16(px, pw, src0->data)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_vec_fused: alignment");
     return launch_gemv_decode((hipStream_t) stream, src0->type, src0->data, src0->ne[0], src0->ne[1], pro, px, pw, eps, epi, dst, nullptr, resid);
 }
 
@@ -488,8 +491,7 @@ extern "C" int cllm_op_moe_router(void * stream, const cllm_tensor * x, const cl
         FAIL(CLLM_E_UNSUPPORTED, "moe_router: dense F32 vectors, I32 ids");
     if (x->ne[0] != K || norm_w->ne[0] != K || xnorm->ne[0] != K || probs->ne[0] != n || t_nelements(x) != K || t_nelements(xnorm) != K || t_nelements(probs) != n || t_nelements(ids) != k)
         FAIL(CLLM_E_INVALID, "moe_router: shapes (one token)");
-    if (!is_quant_type(gate_w->type) || gate_w->ne[2] != 1 || gate_w->ne[3] != 1 || gate_w->nb[1] != cllm_row_size(gate_w->type, K)) return CLLM_E_UNSUPPORTED;
-    if (((uintptr_t) x->data | (uintptr_t) norm_w->data | (uintptr_t) gate_w->data | (uintptr_t) xnorm->data) & 15) return CLLM_E_UNSUPPORTED;
+    if (!dense_quant_matrix(gate_w) || !aligned16(x->data, norm_w->data, gate_w->data, xnorm->data)) return CLLM_E_UNSUPPORTED;
     if (xnorm->data != x->data && (const char *) xnorm->data < (const char *) x->data + K * 4 && (const char *) x->data < (const char *) xnorm->data + K * 4) FAIL(CLLM_E_INVALID, "moe_router: xnorm overlaps x");
     return launch_moe_router((hipStream_t) stream, gate_w->type, gate_w->data, K, n, (const float *) x->data, (const float *) norm_w->data, eps,
                              (float *) xnorm->data, (float *) probs->data, (int32_t *) ids->data, (int) k);
@@ -518,25 +520,10 @@ extern "C" int cllm_pack_rows(void * stream, void * dst, const void * const * sr
 extern "C" int cllm_bench_mul_mat_id(void * stream, const cllm_tensor * as, const cllm_tensor * b, const cllm_tensor * ids, void * const * ids_datas, int n_ids,
                                      cllm_tensor * dst, void * wdata, size_t wsize, int iters, float * avg_us) {
     if (!as || !b || !ids || !dst || !ids_datas || n_ids <= 0 || iters <= 0 || !avg_us) FAIL(CLLM_E_INVALID, "bench_mul_mat_id: arguments");
-    hipStream_t st = (hipStream_t) stream;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1) HIP_TRY(hipEventRecord(e0, st));
-        const int n = pass == 0 ? 2 : iters;
-        for (int i = 0; i < n; i++) {
-            cllm_tensor id = *ids; id.data = ids_datas[i % n_ids];
-            const int rc = cllm_op_mul_mat_id(stream, as, b, &id, dst, wdata, wsize);
-            if (rc) return rc;
-        }
-    }
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-    *avg_us = ms * 1e3f / (float) iters;
-    return CLLM_OK;
+    return timed_launches((hipStream_t) stream, 2, iters, [&](int i) -> int {
+        cllm_tensor id = *ids; id.data = ids_datas[i % n_ids];
+        return cllm_op_mul_mat_id(stream, as, b, &id, dst, wdata, wsize);
+    }, avg_us);
 }
 
 // times the DECODE form of the mat-vec (activation prologue inside the kernel, exactly what cllm_llama's fused step launches)
@@ -544,23 +531,9 @@ extern "C" int cllm_bench_gemv_fused(void * stream, int wtype, void * const * w_
                                      const float * px, const float * pw, float eps, int epi, float * dst, const float * resid, int iters, float * avg_us) {
     if (!is_quant_type(wtype) || !w_datas || n_w <= 0 || iters <= 0 || !avg_us || !px || !dst || pro < 1 || pro > 3) FAIL(CLLM_E_INVALID, "bench_gemv_fused: arguments");
     hipStream_t st = (hipStream_t) stream;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1) HIP_TRY(hipEventRecord(e0, st));
-        const int n = pass == 0 ? (n_w < 4 ? n_w : 4) : iters;
-        for (int i = 0; i < n; i++) {
-            const int rc = launch_mmvq_fused(st, wtype, w_datas[i % n_w], K, nrows, pro, px, pw, eps, epi, dst, nullptr, resid);
-            if (rc) return rc;
-        }
-    }
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-    *avg_us = ms * 1e3f / (float) iters;
-    return CLLM_OK;
+    return timed_launches(st, n_w < 4 ? n_w : 4, iters, [&](int i) -> int {
+        return launch_mmvq_fused(st, wtype, w_datas[i % n_w], K, nrows, pro, px, pw, eps, epi, dst, nullptr, resid);
+    }, avg_us);
 }
 
 // measurement helper (bench.py `ceilings`): what a pure streaming read reaches on this device -- every lane sums 16-byte loads of a buffer larger than the Infinity Cache
@@ -579,24 +552,18 @@ __global__ void __launch_bounds__(1024) k_bench_read(const u32x4 * __restrict__ 
 extern "C" int cllm_bench_read_bw(void * stream, size_t bytes, int iters, float * gb_per_s) {
     if (!gb_per_s || iters <= 0 || bytes < (1u << 20)) FAIL(CLLM_E_INVALID, "bench_read_bw: arguments");
     hipStream_t st = (hipStream_t) stream;
-    char * buf = nullptr; unsigned * out = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bytes + 16));
-    out = (unsigned *)(buf + (bytes & ~(size_t) 15));
-    HIP_TRY(hipMemsetAsync(buf, 1, bytes + 16, st));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    struct dev_buf { char * p = nullptr; ~dev_buf() { if (p) (void) hipFree(p); } } buf;      // freed on every path
+    HIP_TRY(hipMalloc((void **) &buf.p, bytes + 16));
+    unsigned * out = (unsigned *)(buf.p + (bytes & ~(size_t) 15));
+    HIP_TRY(hipMemsetAsync(buf.p, 1, bytes + 16, st));
     const unsigned grid = (unsigned) device_cu_count() * 2;
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1) HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < (pass == 0 ? 1 : iters); i++) hipLaunchKernelGGL(k_bench_read, dim3(grid), dim3(1024), 0, st, (const u32x4 *) buf, bytes / 16, out);
-    }
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-    HIP_TRY(hipFree(buf));
-    *gb_per_s = (float)((double)(bytes / 16 * 16) * iters / (ms * 1e-3) / 1e9);
+    float avg_us = 0.0f;
+    const int rc = timed_launches(st, 1, iters, [&](int) -> int {
+        hipLaunchKernelGGL(k_bench_read, dim3(grid), dim3(1024), 0, st, (const u32x4 *) buf.p, bytes / 16, out);
+        return CLLM_OK;
+    }, &avg_us);
+    if (rc) return rc;
+    *gb_per_s = (float)((double)(bytes / 16 * 16) / ((double) avg_us * 1e-6) / 1e9);
     return CLLM_OK;
 }
 
@@ -609,8 +576,7 @@ extern "C" int cllm_op_mul_mat_id_silu_mul(void * stream, const cllm_tensor * as
     const int64_t n_used = ids->ne[0];
     if (ids->ne[1] != 1 || as_gu->ne[0] != b->ne[0] || as_gu->ne[1] % 2 || dst->ne[0] != as_gu->ne[1] / 2 || dst->ne[1] != n_used || dst->ne[2] != 1 || b->ne[2] != 1 ||
         (b->ne[1] != 1 && b->ne[1] != n_used)) FAIL(CLLM_E_INVALID, "mul_mat_id_silu_mul: shapes (one token)");
-    if (ids->nb[0] != 4 || b->nb[0] != 4 || dst->nb[0] != 4 || as_gu->nb[1] != cllm_row_size(as_gu->type, as_gu->ne[0]) || b->nb[1] % 16 || dst->nb[1] % 4 ||
-        ((uintptr_t) b->data & 15) || ((uintptr_t) as_gu->data & 15) || as_gu->nb[2] % 16) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_id_silu_mul: layout");
+    if (ids->nb[0] != 4 || b->nb[0] != 4 || dst->nb[0] != 4 || !dense_quant_rows(as_gu) || b->nb[1] % 16 || dst->nb[1] % 4 || !aligned16(b->data, as_gu->data, as_gu->nb[2])) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_id_silu_mul: layout");
     return launch_gemv_decode_id((hipStream_t) stream, as_gu->type, as_gu->data, as_gu->nb[2], as_gu->ne[0], as_gu->ne[1], (const float *) b->data,
                                  b->ne[1] == 1 ? 0 : (int64_t)(b->nb[1] / 4), (const int32_t *) ids->data, (int) n_used, (float *) dst->data, (int64_t)(dst->nb[1] / 4), 1);
 }
@@ -627,9 +593,8 @@ extern "C" int cllm_op_moe_router_gate_up(void * stream, const cllm_tensor * x, 
         x->nb[0] != 4 || norm_w->nb[0] != 4 || probs->nb[0] != 4 || ids->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "moe_router_gate_up: dense F32 vectors, I32 ids");
     if (x->ne[0] != K || t_nelements(x) != K || norm_w->ne[0] != K || probs->ne[0] != E || t_nelements(probs) != E || t_nelements(ids) != k || as_gu->ne[0] != K || as_gu->ne[2] != E ||
         as_gu->ne[1] % 2 || dst->ne[0] != as_gu->ne[1] / 2 || dst->ne[1] != k || dst->ne[2] != 1) FAIL(CLLM_E_INVALID, "moe_router_gate_up: shapes (one token)");
-    if (!is_quant_type(gate_w->type) || gate_w->type != as_gu->type || gate_w->ne[2] != 1 || gate_w->ne[3] != 1 || gate_w->nb[1] != cllm_row_size(gate_w->type, K) ||
-        as_gu->nb[1] != cllm_row_size(as_gu->type, K) || as_gu->nb[2] % 16 || dst->nb[1] % 4) return CLLM_E_UNSUPPORTED;
-    if (((uintptr_t) x->data | (uintptr_t) norm_w->data | (uintptr_t) gate_w->data | (uintptr_t) as_gu->data) & 15) return CLLM_E_UNSUPPORTED;
+    if (!dense_quant_matrix(gate_w) || gate_w->type != as_gu->type || !dense_quant_rows(as_gu) || dst->nb[1] % 4) return CLLM_E_UNSUPPORTED;
+    if (!aligned16(x->data, norm_w->data, gate_w->data, as_gu->data, as_gu->nb[2])) return CLLM_E_UNSUPPORTED;
     return launch_gemv_decode_id_router_silu((hipStream_t) stream, as_gu->type, as_gu->data, as_gu->nb[2], K, as_gu->ne[1], (const float *) x->data, (const float *) norm_w->data, eps,
                                              gate_w->data, (int) E, (int) k, (float *) probs->data, (int32_t *) ids->data, (float *) dst->data, (int64_t)(dst->nb[1] / 4));
 }
@@ -647,8 +612,7 @@ extern "C" int cllm_op_mul_mat_id_combine(void * stream, const cllm_tensor * as,
     if (b->ne[0] != K || b->ne[2] != 1 || b->ne[3] != 1 || ids->ne[1] != 1 || t_nelements(ids) != ids->ne[0] || probs->ne[0] != E || t_nelements(probs) != E || dst->ne[0] != H || t_nelements(dst) != H ||
         (resid && (resid->ne[0] != H || t_nelements(resid) != H))) FAIL(CLLM_E_INVALID, "mul_mat_id_combine: shapes (one token)");
     if (ids->ne[0] != 2 || b->ne[1] != 2) return CLLM_E_UNSUPPORTED;
-    if (ids->nb[0] != 4 || b->nb[0] != 4 || dst->nb[0] != 4 || probs->nb[0] != 4 || (resid && resid->nb[0] != 4) || as->nb[1] != cllm_row_size(as->type, K) || b->nb[1] % 16 ||
-        ((uintptr_t) b->data & 15) || ((uintptr_t) as->data & 15) || as->nb[2] % 16) return CLLM_E_UNSUPPORTED;
+    if (ids->nb[0] != 4 || b->nb[0] != 4 || dst->nb[0] != 4 || probs->nb[0] != 4 || (resid && resid->nb[0] != 4) || !dense_quant_rows(as) || b->nb[1] % 16 || !aligned16(b->data, as->data, as->nb[2])) return CLLM_E_UNSUPPORTED;
     return launch_gemv_decode_id_combine((hipStream_t) stream, as->type, as->data, as->nb[2], K, H, (const float *) b->data, (int64_t)(b->nb[1] / 4), (const int32_t *) ids->data,
                                          (const float *) probs->data, resid ? (const float *) resid->data : nullptr, (float *) dst->data);
 }
@@ -668,11 +632,10 @@ extern "C" int cllm_op_mul_mat_id(void * stream, const cllm_tensor * as, const c
     const size_t stride = act_row_bytes(as->ne[0], kind);
     const size_t need = stride * (size_t) t_nrows(b);
     if (!wdata || wsize < need) FAIL(CLLM_E_INVALID, "mul_mat_id: wdata too small (%zu < %zu)", wsize, need);
-    if (as->type == CLLM_TYPE_Q4_K && ((uintptr_t) as->data % 16 || as->nb[1] % 16 || as->nb[2] % 16)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_id: alignment");
+    if (as->type == CLLM_TYPE_Q4_K && !rows_aligned(as, 2)) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_id: alignment");
     hipStream_t st = (hipStream_t) stream;
     // one token (decode): the decode mat-vec with the expert picked per grid slice, activation quantized inside (one launch per MUL_MAT_ID)
-    if (n_tok == 1 && ids->nb[0] == 4 && b->nb[0] == 4 && dst->nb[0] == 4 && as->nb[1] == cllm_row_size(as->type, as->ne[0]) && b->nb[1] % 16 == 0 && dst->nb[1] % 4 == 0 &&
-        ((uintptr_t) b->data & 15) == 0 && ((uintptr_t) as->data & 15) == 0 && as->nb[2] % 16 == 0) {
+    if (n_tok == 1 && ids->nb[0] == 4 && b->nb[0] == 4 && dst->nb[0] == 4 && as->nb[1] == cllm_row_size(as->type, as->ne[0]) && b->nb[1] % 16 == 0 && dst->nb[1] % 4 == 0 && aligned16(b->data, as->data, as->nb[2])) {
         rc = launch_gemv_decode_id(st, as->type, as->data, as->nb[2], as->ne[0], as->ne[1], (const float *) b->data, b->ne[1] == 1 ? 0 : (int64_t)(b->nb[1] / 4),
                                    (const int32_t *) ids->data, (int) n_used, (float *) dst->data, (int64_t)(dst->nb[1] / 4));
         if (rc != CLLM_E_UNSUPPORTED) return rc;

@@ -10,6 +10,7 @@
 #include "glibc_math.h"
 #include "norm_order.h"
 #include "options.h"
+#include "types.h"
 
 #define CLLM_WAVE 64
 
@@ -31,7 +32,6 @@ struct __attribute__((packed)) block_q4_K { uint16_t d, dmin; uint8_t scales[12]
 struct __attribute__((packed)) block_q8_K { float d; int8_t qs[256]; int16_t bsums[16]; };      // 292 B
 struct __attribute__((packed)) block_q5_K { uint16_t d, dmin; uint8_t scales[12]; uint8_t qh[32]; uint8_t qs[128]; };   // 176 B (ggml-common.h:308-321)
 struct __attribute__((packed)) block_q6_K { uint8_t ql[128]; uint8_t qh[64]; int8_t scales[16]; uint16_t d; };          // 210 B (ggml-common.h:323-336)
-static_assert(sizeof(block_q5_K) == 176 && sizeof(block_q6_K) == 210, "block sizes");
 // the other formats stock model files carry (ggml-common.h:190-216, 262-288, 415-419): mat-mul through gemv_kq.hip, GET_ROWS
 struct __attribute__((packed)) block_q5_0   { uint16_t d; uint8_t qh[4]; uint8_t qs[16]; };                  // 22 B: w = ((nib | bit << 4) - 16) * d
 struct __attribute__((packed)) block_q5_1   { uint16_t d, m; uint8_t qh[4]; uint8_t qs[16]; };               // 24 B: w = (nib | bit << 4) * d + m
@@ -39,13 +39,16 @@ struct __attribute__((packed)) block_iq4_nl { uint16_t d; uint8_t qs[16]; };    
 struct __attribute__((packed)) block_iq4_xs { uint16_t d, scales_h; uint8_t scales_l[4]; uint8_t qs[128]; };  // 136 B: 256 weights, w = kvalues_iq4nl[nib] * d * (ls - 32), a 6-bit ls per 32 (ggml-common.h:421-427)
 struct __attribute__((packed)) block_tq1_0  { uint8_t qs[48]; uint8_t qh[4]; uint16_t d; };                   // 54 B: 256 ternary weights, 5 per byte of qs (base 3), 4 per byte of qh: w = (trit - 1) * d (ggml-common.h:241-249)
 struct __attribute__((packed)) block_tq2_0  { uint8_t qs[64]; uint16_t d; };                                  // 66 B: 256 ternary weights, 2 bits each: w = (q - 1) * d (ggml-common.h:251-256)
-static_assert(sizeof(block_tq1_0) == 54 && sizeof(block_tq2_0) == 66, "block sizes");
 struct __attribute__((packed)) block_mxfp4  { uint8_t e; uint8_t qs[16]; };                                  // 17 B: w = kvalues_mxfp4[nib] * 2^(e - 128)
 struct __attribute__((packed)) block_q2_K   { uint8_t scales[16]; uint8_t qs[64]; uint16_t d, dmin; };       // 84 B
 struct __attribute__((packed)) block_q3_K   { uint8_t hmask[32]; uint8_t qs[64]; uint8_t scales[12]; uint16_t d; };   // 110 B
-static_assert(sizeof(block_q5_0) == 22 && sizeof(block_q5_1) == 24 && sizeof(block_iq4_nl) == 18 && sizeof(block_mxfp4) == 17 && sizeof(block_q2_K) == 84 && sizeof(block_q3_K) == 110 && sizeof(block_iq4_xs) == 136, "block sizes");
-static_assert(sizeof(block_q4_1) == 20 && sizeof(block_q8_1) == 36, "block sizes");
-static_assert(sizeof(block_q4_0) == 18 && sizeof(block_q8_0) == 34 && sizeof(block_q4_K) == 144 && sizeof(block_q8_K) == 292, "block sizes");
+static_assert(sizeof(block_q8_1) == 36 && sizeof(block_q8_K) == 292, "block sizes");      // the activation formats: no rows of types.def
+// every weight format with a struct above, against its row of types.def
+#define WT_BLOCK(name, S) static_assert(wtype_size(CLLM_TYPE_##name) == sizeof(S), "types.def: block_bytes of " #name)
+WT_BLOCK(Q4_0, block_q4_0); WT_BLOCK(Q4_1, block_q4_1); WT_BLOCK(Q8_0, block_q8_0); WT_BLOCK(Q4_K, block_q4_K); WT_BLOCK(Q5_K, block_q5_K); WT_BLOCK(Q6_K, block_q6_K);
+WT_BLOCK(Q5_0, block_q5_0); WT_BLOCK(Q5_1, block_q5_1); WT_BLOCK(IQ4_NL, block_iq4_nl); WT_BLOCK(IQ4_XS, block_iq4_xs); WT_BLOCK(TQ1_0, block_tq1_0); WT_BLOCK(TQ2_0, block_tq2_0);
+WT_BLOCK(MXFP4, block_mxfp4); WT_BLOCK(Q2_K, block_q2_K); WT_BLOCK(Q3_K, block_q3_K);
+#undef WT_BLOCK
 
 // ---- device-side activation layout ("act row") -------------------------------------------------
 // The CPU path converts each src1 row to the weight's vec_dot_type before the dot products
@@ -55,23 +58,13 @@ static_assert(sizeof(block_q4_0) == 18 && sizeof(block_q8_0) == 34 && sizeof(blo
 //   Q8_K kind (for Q4_K weights):       qs[K] int8 | d[K/256] f32                      | s[K/32] int32 (sum per 32)
 //   Q8_1 kind (for Q4_1 weights):       the Q8_0 planes, but s[K/32] is an f32: fp16(d_unrounded * sum of qs), block_q8_1::s
 // Each plane starts 16-byte aligned; act_row_bytes() is the per-row stride.  A "kind" is the quantization block size (32 / 256);
-// ACT_Q8_1 names the third flavour and maps to block size 32.
-enum { ACT_Q8_0 = 32, ACT_Q8_K = 256, ACT_Q8_1 = 33 };
+// ACT_Q8_1 names the third flavour and maps to block size 32 (the enum: types.h).
 __host__ __device__ inline int    act_blk(int kind) { return kind == ACT_Q8_1 ? 32 : kind; }
 __host__ __device__ inline size_t act_align16(size_t x) { return (x + 15) & ~(size_t) 15; }
 __host__ __device__ inline size_t act_off_d(int64_t K) { return act_align16((size_t) K); }
 __host__ __device__ inline size_t act_off_s(int64_t K, int kind) { return act_off_d(K) + act_align16((size_t)(K / act_blk(kind)) * 4); }
 __host__ __device__ inline size_t act_row_bytes(int64_t K, int kind) { return act_off_s(K, kind) + act_align16((size_t)(K / 32) * 4); }
-// the activation format a weight type's dot product reads (type_traits_cpu[].vec_dot_type, ggml-cpu/ggml-cpu.c:207-390)
-// the codebook ("grid") formats IQ2_XXS / IQ2_XS / IQ2_S / IQ3_XXS / IQ3_S (ggml-common.h:346-390; block sizes 66 / 74 / 82 / 98 / 110 bytes, fp16 d first; codebooks: iq_grids.h)
-__host__ __device__ inline bool   is_iq_grid_type(int t) { return t == CLLM_TYPE_IQ2_XXS || t == CLLM_TYPE_IQ2_XS || t == CLLM_TYPE_IQ2_S || t == CLLM_TYPE_IQ3_XXS || t == CLLM_TYPE_IQ3_S; }
-// the coverage types (gemv_kq.hip: mat-mul for any number of columns in the reference's order, GET_ROWS; no fused decode forms)
-__host__ __device__ inline bool   is_kq_type(int t) {
-    return t == CLLM_TYPE_Q5_K || t == CLLM_TYPE_Q6_K || t == CLLM_TYPE_Q2_K || t == CLLM_TYPE_Q3_K || t == CLLM_TYPE_Q5_0 || t == CLLM_TYPE_Q5_1 || t == CLLM_TYPE_IQ4_NL || t == CLLM_TYPE_MXFP4 || t == CLLM_TYPE_IQ4_XS || t == CLLM_TYPE_TQ1_0 || t == CLLM_TYPE_TQ2_0 || is_iq_grid_type(t) || t == CLLM_TYPE_IQ1_S || t == CLLM_TYPE_IQ1_M;
-}
-__host__ __device__ inline bool   is_k256_type(int t) { return t == CLLM_TYPE_Q4_K || t == CLLM_TYPE_Q5_K || t == CLLM_TYPE_Q6_K || t == CLLM_TYPE_Q2_K || t == CLLM_TYPE_Q3_K || t == CLLM_TYPE_IQ4_XS || t == CLLM_TYPE_TQ1_0 || t == CLLM_TYPE_TQ2_0 || is_iq_grid_type(t) || t == CLLM_TYPE_IQ1_S || t == CLLM_TYPE_IQ1_M; }
-__host__ __device__ inline int    act_kind_of(int wtype) { return is_k256_type(wtype) ? ACT_Q8_K : (wtype == CLLM_TYPE_Q4_1 || wtype == CLLM_TYPE_Q5_1) ? ACT_Q8_1 : ACT_Q8_0; }
-__host__ __device__ inline bool   is_quant_type(int t) { return t == CLLM_TYPE_Q4_0 || t == CLLM_TYPE_Q4_1 || t == CLLM_TYPE_Q8_0 || t == CLLM_TYPE_Q4_K; }
+// which activation format a weight type's dot product reads, the coverage types and the codebook ("grid") formats: act_kind_of(), is_kq_type(), is_iq_grid_type() of types.h
 
 // ---- small device helpers -----------------------------------------------------------------------
 #ifdef __HIPCC__

@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr bool IS_K = TYPE == CLLM_TYPE_Q4_K, IS_41 = TYPE == CLLM_TYPE_Q4_1, IS_Q8 = TYPE == CLLM_TYPE_Q8_0;
     constexpr int STAGE = (BN + BM) * MMD_LD, WM = BM / 2, WN = BN / 2, MI = WM / 32, NJ = WN / 32, WT = BN / 128, XT = BM / 32;
-    constexpr int BS = IS_Q8 ? 34 : IS_41 ? 20 : 18, QOFF = IS_41 ? 4 : 2;
+    constexpr int BS = (int) wtype_size(TYPE), QOFF = IS_41 ? 4 : 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned mt, nt;
     gemm_tile_of(blockIdx.x, (unsigned)((a.M + BM - 1) / BM), (unsigned)((a.N + BN - 1) / BN), 4, mt, nt);
@@ -247,19 +247,15 @@ int launch_dense_f16(hipStream_t st, int wtype, const tview & w, const tview & x
     if (g_mmd_tile < 0) g_mmd_tile = opt_int(OPT_CLLM_MMD_TILE);  // tests / tools: 128 / 256 force
     const int64_t big_tiles = ((M + 255) / 256) * ((N + 255) / 256);
     const bool big = g_mmd_tile == 256;
-#define GO(T) do { \
-        if (big) { constexpr int LDS = 2 * 512 * MMD_LD; static uint64_t attr = 0; \
-            if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmd<T, 256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); } \
-            hipLaunchKernelGGL((k_mmd<T, 256, 256>), dim3((unsigned) big_tiles), dim3(256), LDS, st, a); } \
-        else { constexpr int LDS = 2 * 256 * MMD_LD; static uint64_t attr = 0; \
-            if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmd<T, 128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); } \
-            hipLaunchKernelGGL((k_mmd<T, 128, 128>), dim3((unsigned)(((M + 127) / 128) * ((N + 127) / 128))), dim3(256), LDS, st, a); } } while (0)
-    if (wtype == CLLM_TYPE_Q4_K) GO(CLLM_TYPE_Q4_K);
-    else if (wtype == CLLM_TYPE_Q4_0) GO(CLLM_TYPE_Q4_0);
-    else if (wtype == CLLM_TYPE_Q8_0) GO(CLLM_TYPE_Q8_0);
-    else if (wtype == CLLM_TYPE_Q4_1) GO(CLLM_TYPE_Q4_1);
-    else return CLLM_E_UNSUPPORTED;
-#undef GO
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    return with_tuned_type(wtype, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
+        if (big) { constexpr int LDS = 2 * 512 * MMD_LD; static uint64_t attr = 0;
+            if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmd<T, 256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
+            hipLaunchKernelGGL((k_mmd<T, 256, 256>), dim3((unsigned) big_tiles), dim3(256), LDS, st, a); }
+        else { constexpr int LDS = 2 * 256 * MMD_LD; static uint64_t attr = 0;
+            if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmd<T, 128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
+            hipLaunchKernelGGL((k_mmd<T, 128, 128>), dim3((unsigned)(((M + 127) / 128) * ((N + 127) / 128))), dim3(256), LDS, st, a); }
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    });
 }

@@ -54,6 +54,9 @@ __device__ __forceinline__ float iq1m_d(const char * blk) {          // the fp16
     const uint8_t * b8 = (const uint8_t *) blk + 48;
     return h2f((uint16_t)((b8[1] >> 4) | (b8[3] & 0xf0) | ((uint32_t)(b8[5] & 0xf0) << 4) | ((uint32_t)(b8[7] & 0xf0) << 8)));
 }
+// block_bytes of a NAMED row of types.def.  Inside a case that serves several types the rows are picked by name: wtype_size() of the run-time type is a second
+// switch there, which cost k_argmax_final_next (the greedy step's embedding row) three SGPRs and 600 bytes.
+#define DQ_BS(name) ((int) wtype_size(CLLM_TYPE_##name))
 __device__ __forceinline__ float dequant_elem(int type, const char * row, int64_t i) {
     switch (type) {
         case CLLM_TYPE_F32: return ((const float *) row)[i];
@@ -102,7 +105,7 @@ __device__ __forceinline__ float dequant_elem(int type, const char * row, int64_
         }
         case CLLM_TYPE_Q5_0: case CLLM_TYPE_Q5_1: {   // dequantize_row_q5_0 / _q5_1 (ggml-quants.c:348-399)
             const bool q51 = type == CLLM_TYPE_Q5_1;
-            const uint8_t * b = (const uint8_t *) row + (i / 32) * (q51 ? 24 : 22); const int j = (int)(i % 32);
+            const uint8_t * b = (const uint8_t *) row + (i / 32) * (q51 ? DQ_BS(Q5_1) : DQ_BS(Q5_0)); const int j = (int)(i % 32);
             const uint8_t * qh = b + (q51 ? 4 : 2), * qs = qh + 4;
             const uint32_t h = (uint32_t) qh[0] | ((uint32_t) qh[1] << 8) | ((uint32_t) qh[2] << 16) | ((uint32_t) qh[3] << 24);
             const int q = (j < 16 ? (qs[j] & 0xF) : (qs[j - 16] >> 4)) | (int)(((h >> j) & 1u) << 4);
@@ -111,7 +114,7 @@ __device__ __forceinline__ float dequant_elem(int type, const char * row, int64_
         }
         case CLLM_TYPE_IQ4_NL: case CLLM_TYPE_MXFP4: {   // dequantize_row_iq4_nl / _mxfp4 (ggml-quants.c:2512-2528, 417-436)
             const bool mx = type == CLLM_TYPE_MXFP4;
-            const uint8_t * b = (const uint8_t *) row + (i / 32) * (mx ? 17 : 18); const int j = (int)(i % 32);
+            const uint8_t * b = (const uint8_t *) row + (i / 32) * (mx ? DQ_BS(MXFP4) : DQ_BS(IQ4_NL)); const int j = (int)(i % 32);
             const uint8_t * qs = b + (mx ? 1 : 2);
             const int nib = j < 16 ? (qs[j] & 0xF) : (qs[j - 16] >> 4);
             const uint64_t tab = mx ? (nib < 8 ? 0x0c08060403020100ull : 0xf4f8fafcfdfeff00ull) : (nib < 8 ? 0xf6eaddcfbfad9881ull : 0x7159453526190d01ull);
@@ -129,7 +132,7 @@ __device__ __forceinline__ float dequant_elem(int type, const char * row, int64_
             return dl * (float)(int8_t)((tab >> (8 * (nib & 7))) & 0xff);
         }
         case CLLM_TYPE_IQ1_S: case CLLM_TYPE_IQ1_M: {  // dequantize_row_iq1_s / _iq1_m (ggml-quants.c:2464-2536): y = dl * (value + delta), dl = d * (2 s + 1), delta = +-0.125f
-            const char * blk = row + (i / 256) * (type == CLLM_TYPE_IQ1_S ? 50 : 56); const int e = (int)(i % 256), ib = e / 32, l = (e % 32) / 8, half = (e % 8) / 4, k = e % 4;
+            const char * blk = row + (i / 256) * (type == CLLM_TYPE_IQ1_S ? DQ_BS(IQ1_S) : DQ_BS(IQ1_M)); const int e = (int)(i % 256), ib = e / 32, l = (e % 32) / 8, half = (e % 8) / 4, k = e % 4;
             int ls; bool neg;
             const uint32_t w4 = iq1_w4(type, blk, ib, l, half, ls, neg);
             const float d = type == CLLM_TYPE_IQ1_S ? h2f(*(const uint16_t *) blk) : iq1m_d(blk);
@@ -138,7 +141,7 @@ __device__ __forceinline__ float dequant_elem(int type, const char * row, int64_
         case CLLM_TYPE_IQ2_XXS: case CLLM_TYPE_IQ2_XS: case CLLM_TYPE_IQ2_S: case CLLM_TYPE_IQ3_XXS: case CLLM_TYPE_IQ3_S: {
             // dequantize_row_iq2_xxs / _iq2_xs / _iq2_s / _iq3_xxs / _iq3_s (ggml-quants.c:2275-2460): y = db * magnitude * (+-1.f), db = d * (0.5f + ls) * 0.25f (IQ2), * 0.5f
             // (IQ3_XXS), d * (1 + 2 ls) (IQ3_S) -- in these operation orders
-            const int bs = type == CLLM_TYPE_IQ2_XXS ? 66 : type == CLLM_TYPE_IQ2_XS ? 74 : type == CLLM_TYPE_IQ2_S ? 82 : type == CLLM_TYPE_IQ3_XXS ? 98 : 110;
+            const int bs = type == CLLM_TYPE_IQ2_XXS ? DQ_BS(IQ2_XXS) : type == CLLM_TYPE_IQ2_XS ? DQ_BS(IQ2_XS) : type == CLLM_TYPE_IQ2_S ? DQ_BS(IQ2_S) : type == CLLM_TYPE_IQ3_XXS ? DQ_BS(IQ3_XXS) : DQ_BS(IQ3_S);
             const char * blk = row + (i / 256) * bs; const int e = (int)(i % 256), ib = e / 32, l = (e % 32) / 8, half = (e % 8) / 4, k = e % 4;
             int ls_lo, ls_hi;
             const uint32_t w4 = iq_grid_w4(type, blk, ib, l, half, ls_lo, ls_hi);
@@ -180,3 +183,4 @@ __device__ __forceinline__ float dequant_elem(int type, const char * row, int64_
     }
     return 0.0f;
 }
+#undef DQ_BS

@@ -32,7 +32,7 @@ int launch_gemv_decode(hipStream_t st, int wtype, const void * W, int64_t K, int
     if (epi == 1 && (pro != 1 || !gate_up_pairs_ok(nrows) || bias || resid)) FAIL(CLLM_E_UNSUPPORTED, "gemv_decode: SiLU epilogue needs gate/up row pairs, features %% 8 == 0");
     gemv_dec_args a;
     a.px = px; a.pw = pw; a.padd = padd; a.W = (const char *) W; a.eps = eps; a.dst = dst; a.xout = xout; a.bias = bias; a.resid = resid; a.ts = g_gemv_ts;
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         const int npre = p.npre;
         if (pro == 1 && epi == 1) return npre == 1 ? gemv_dec_launch<FMT, 1, 1, 1>(st, p, a) : gemv_dec_launch<FMT, 1, 1, 4>(st, p, a);
@@ -55,7 +55,7 @@ int launch_gemv_decode_id(hipStream_t st, int wtype, const void * W, size_t w_ex
     gemv_dec_args a;
     a.px = px; a.W = (const char *) W; a.dst = dst; a.w_expert_bytes = w_expert_bytes;
     a.moe_ids(ids); a.act_slot_stride(px_slot_stride); a.out_slot_stride(dst_slot_stride);
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         const int npre = p.npre;
         if (epi == 1) return npre == 1 ? gemv_dec_launch<FMT, 2, 1, 1, true>(st, p, a) : npre == 4 ? gemv_dec_launch<FMT, 2, 1, 4, true>(st, p, a) : gemv_dec_launch<FMT, 2, 1, 8, true>(st, p, a);

@@ -3,7 +3,7 @@
 //   gemv_dec_form / gemv_dec_plan + gemv_dec_make_plan()  the shape refusals every form shares, the ONE LDS sum (refused and launched with), the deal of units to waves, npre
 //   gemv_dec_args                         the kernel's arguments by name; the three slots a family overloads are set through setters named as the kernel names them
 //   gemv_dec_launch<...>()                the attribute (once per device and instantiation) + the launch
-//   gemv_dec_by_type()                    the four-way ladder over the weight type
+// The four-way ladder over the weight type is with_tuned_type() of types.h: leaf(std::integral_constant<int, FMT>), the leaf names the (PRO, EPI, NPRE) forms of its launcher.
 // Host code only: which instantiations a translation unit holds, and in which order, is decided by the leaves its launchers name -- see gemv_decode.hip on why that matters.
 #include <type_traits>
 #include "gemv_decode_kernel.h"
@@ -20,7 +20,7 @@ struct gemv_dec_form { int64_t k_max = 0, units = 0, grid_cap = 1; int grid_y = 
 // false: CLLM_E_UNSUPPORTED.  (Within every form's K bound the LDS sum stays below the limit -- 129280 bytes at most, the combine of a 32-weight format at K 32768:
 //  tests/moe_model.py -- so that refusal decides nothing today; it is the guard of the next form.)
 static inline bool gemv_dec_make_plan(gemv_dec_plan & p, int wtype, int64_t K, int64_t nrows, const gemv_dec_form & f) {
-    const int kind = wtype == CLLM_TYPE_Q4_K ? 256 : 32;
+    const int kind = wtype_blck(wtype);
     if (!is_quant_type(wtype) || K % kind || K > f.k_max || nrows <= 0 || (uint64_t) nrows * (uint64_t) cllm_row_size(wtype, K) >= (1ull << 32)) return false;
     p.lds = f.act_rows * act_row_bytes(K, kind) + 16 * (size_t)(wtype == CLLM_TYPE_Q4_K ? Q4K_CHAIN_BYTES : Q32_CHAIN_BYTES) + f.extra_lds;
     if (p.lds > K_GEMV_DEC_MAX_DYN_LDS) return false;
@@ -73,13 +73,4 @@ static int gemv_dec_launch(hipStream_t st, const gemv_dec_plan & p, const gemv_d
                        a.dst, a.xout, a.bias, a.resid, a.ts, a.ids, a.w_expert_bytes, a.px_slot_stride, a.dst_slot_stride);
     LAUNCH_CHECK();
     return CLLM_OK;
-}
-
-// leaf(std::integral_constant<int, FMT>) for the plan's weight type (gemv_dec_make_plan has refused every other); the leaf names the (PRO, EPI, NPRE) forms of its launcher
-template <class Leaf>
-static int gemv_dec_by_type(int wtype, Leaf && leaf) {
-    if (wtype == CLLM_TYPE_Q4_K) return leaf(std::integral_constant<int, CLLM_TYPE_Q4_K>());
-    if (wtype == CLLM_TYPE_Q4_0) return leaf(std::integral_constant<int, CLLM_TYPE_Q4_0>());
-    if (wtype == CLLM_TYPE_Q4_1) return leaf(std::integral_constant<int, CLLM_TYPE_Q4_1>());
-    return leaf(std::integral_constant<int, CLLM_TYPE_Q8_0>());
 }

@@ -22,7 +22,7 @@ int launch_gemv_decode_free(hipStream_t st, int wtype, const void * W, int64_t K
     if (!gemv_dec_make_plan(p, wtype, K, nrows, f)) return CLLM_E_UNSUPPORTED;
     gemv_dec_args a;
     a.px = px; a.pw = pw; a.W = (const char *) W; a.eps = eps; a.dst = dst; a.bias = bias; a.resid = resid;
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         if constexpr (FMT == CLLM_TYPE_Q4_K) return CLLM_E_UNSUPPORTED;      // (refused above: the free-order tier has no Q4_K instantiation)
         else {

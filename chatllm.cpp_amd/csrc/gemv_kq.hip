@@ -55,6 +55,7 @@ __device__ __forceinline__ uint32_t lut16(uint32_t idx, uint32_t t0, uint32_t t1
 }
 template <int TYPE, int NC>
 __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
+    constexpr int BS = (int) wtype_size(TYPE);
     const int tid = blockIdx.x * 256 + threadIdx.x, A = tid & 7;
     int row = tid >> 3;
     const bool live = row < a.N;                       // whole waves stay: the final lane exchanges read their neighbours
@@ -71,7 +72,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
         int aoff[8];
         float dw, dmin = 0.0f; int mn[8];
         if (TYPE == CLLM_TYPE_Q5_K) {
-            const char * blk = wr + (int64_t) b * 176;
+            const char * blk = wr + (int64_t) b * BS;
             const u32x4 h = *(const u32x4 *) blk;
             dw = h2f((uint16_t)(h.x & 0xffff)); dmin = h2f((uint16_t)(h.x >> 16));
             const uint32_t u0 = h.y & 0x3f3f3f3fu, u2 = h.z & 0x3f3f3f3fu;                          // get_scale_min_k4 (ggml-quants.c:703-711)
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
             // term t = 4 n + j: plane j (bits 2j) of the 32-byte vector of the n-th 128 weights, bytes 4A..4A+3, against activations 128 n + 32 j + 4A..; its scale is the one of
             // the 16-weight sub-block the bytes lie in: index 8 n + 2 j + (A >> 2)
             constexpr bool Q2 = TYPE == CLLM_TYPE_Q2_K;
-            const char * blk = wr + (int64_t) b * (Q2 ? 84 : 110);
+            const char * blk = wr + (int64_t) b * BS;
             dw = h2f(*(const uint16_t *)(blk + (Q2 ? 80 : 108)));
             int8_t s16[16];
             if (Q2) {
@@ -130,7 +131,6 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
             if (Q2) { mn[0] = ((uint8_t) s16[2 * A]) >> 4; mn[1] = ((uint8_t) s16[2 * A + 1]) >> 4; }
         } else if (is_iq_grid_type(TYPE)) {
             // sub-block ib, lane A: the 8-group l = A >> 1, its half A & 1 -> four signed magnitudes; the scale of the lane's 16: 2 ls + 1
-            constexpr int BS = TYPE == CLLM_TYPE_IQ2_XXS ? 66 : TYPE == CLLM_TYPE_IQ2_XS ? 74 : TYPE == CLLM_TYPE_IQ2_S ? 82 : TYPE == CLLM_TYPE_IQ3_XXS ? 98 : 110;
             const char * blk = wr + (int64_t) b * BS;
             dw = h2f(*(const uint16_t *) blk);
 #pragma unroll
@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
             }
         } else if (TYPE == CLLM_TYPE_IQ1_S || TYPE == CLLM_TYPE_IQ1_M) {
             // sub-block ib, lane A: 8-group l = A >> 1, half A & 1 -> four values in {-1, 0, 1}; mn[ib] = the group's scale with the delta's sign (IQ1_M: per lane; IQ1_S: per sub-block)
-            const char * blk = wr + (int64_t) b * (TYPE == CLLM_TYPE_IQ1_S ? 50 : 56);
+            const char * blk = wr + (int64_t) b * BS;
             dw = TYPE == CLLM_TYPE_IQ1_S ? h2f(*(const uint16_t *) blk) : iq1m_d(blk);
 #pragma unroll
             for (int ib = 0; ib < 8; ib++) {
@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
             }
         } else if (TYPE == CLLM_TYPE_TQ2_0) {
             // plane l (bits 2l) of the j-th 32 bytes = elements 128 j + 32 l + (0..31): lane A takes bytes 4A..4A+3 of every plane; the weight is q - 1, the "- 1" comes off below
-            const char * blk = wr + (int64_t) b * 66;
+            const char * blk = wr + (int64_t) b * BS;
             dw = h2f(*(const uint16_t *)(blk + 64));
 #pragma unroll
             for (int j = 0; j < 2; j++) {
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
         } else if (TYPE == CLLM_TYPE_TQ1_0) {
             // chunk c of 32 elements: c < 5: plane c of qs[0..31] (bytes 4A..); c = 5, 6: planes (0, 1), (2, 3) of qs[32..47] (the low half of the chunk from the even plane);
             // c = 7: plane 4 of qs[32..47], then the 16 elements of qh (plane A - 4 of its 4 bytes).  trit = ((byte * 3^n mod 256) * 3) >> 8 per byte, two 16-bit fields at a time
-            const char * blk = wr + (int64_t) b * 54;
+            const char * blk = wr + (int64_t) b * BS;
             dw = h2f(*(const uint16_t *)(blk + 52));
             const uint32_t B0 = ld2(blk + 4 * A), B1 = ld2(blk + 32 + 4 * (A & 3)), QH = ld2(blk + 48);
             auto trits = [](uint32_t bytes4, uint32_t p) -> uint32_t {
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
         } else if (TYPE == CLLM_TYPE_IQ4_XS) {
             // sub-block ib (32 weights = 16 bytes: low nibbles are elements 0..15, high nibbles 16..31): lane A takes elements 4A..4A+3 = the low (A < 4) or high nibbles of
             // bytes 4 (A & 3) ..+3 through the IQ4_NL codebook; its scale is the 6-bit ls - 32 (scales_l nibble | two bits of scales_h)
-            const char * blk = wr + (int64_t) b * 136;
+            const char * blk = wr + (int64_t) b * BS;
             const uint32_t hd = *(const uint32_t *) blk, sl = *(const uint32_t *)(blk + 4);        // d | scales_h << 16, scales_l[4]
             dw = h2f((uint16_t)(hd & 0xffff));
             const uint32_t sh = hd >> 16;
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
                 aoff[ib] = 32 * ib + 4 * A;
             }
         } else {
-            const char * blk = wr + (int64_t) b * 210;
+            const char * blk = wr + (int64_t) b * BS;
             dw = h2f(*(const uint16_t *)(blk + 208));
 #pragma unroll
             for (int j = 0; j < 2; j++) {
@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
 template <int TYPE, int NC, bool CHAIN>
 __global__ void __launch_bounds__(256) k_gemv_b32(const kq_args a) {
     constexpr bool Q50 = TYPE == CLLM_TYPE_Q5_0, Q51 = TYPE == CLLM_TYPE_Q5_1, NL = TYPE == CLLM_TYPE_IQ4_NL, MX = TYPE == CLLM_TYPE_MXFP4;
-    constexpr int BS = Q50 ? 22 : Q51 ? 24 : NL ? 18 : 17, QOFF = Q50 ? 6 : Q51 ? 8 : NL ? 2 : 1;
+    constexpr int BS = (int) wtype_size(TYPE), QOFF = BS - 16;                       // the 16 nibble bytes close every one of these blocks
     const int tid = blockIdx.x * 256 + threadIdx.x, A = tid & 7;
     int row = tid >> 3;
     const bool live = row < a.N;
@@ -334,48 +334,36 @@ __global__ void __launch_bounds__(256) k_gemv_b32(const kq_args a) {
 
 // act: the act rows (launch_quantize_act, kind act_kind_of(wtype)) of the M columns; dst[m * ldd + n]
 static int kq_check(int wtype, const tview & w, int64_t K, int64_t N) {
-    const bool k256 = is_k256_type(wtype);
-    if (!is_kq_type(wtype) || K % (k256 ? 256 : 32) || N <= 0 || N > (1 << 28)) return CLLM_E_UNSUPPORTED;
+    if (!is_kq_type(wtype) || K % wtype_blck(wtype) || N <= 0 || N > (1 << 28)) return CLLM_E_UNSUPPORTED;
     const uintptr_t al = (uintptr_t) w.data | (uintptr_t) w.nb[1] | (uintptr_t) w.nb[2];
-    if (wtype == CLLM_TYPE_Q5_K ? (al & 15) : wtype == CLLM_TYPE_IQ4_XS ? (al & 3) : wtype == CLLM_TYPE_MXFP4 ? 0 : (al & 1)) return CLLM_E_UNSUPPORTED;
+    if (al & (uintptr_t)(wtype_row_align(wtype) - 1)) return CLLM_E_UNSUPPORTED;
     return CLLM_OK;
 }
+// the NC 1 / 4 / 8 instantiation for a.ncols columns
+template <class K1, class K4, class K8>
+static int kq_launch_nc(hipStream_t st, const kq_args & a, dim3 grid, K1 k1, K4 k4, K8 k8) {
+    if (a.ncols == 1) hipLaunchKernelGGL(k1, grid, dim3(256), 0, st, a);
+    else if (a.ncols <= 4) hipLaunchKernelGGL(k4, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k8, grid, dim3(256), 0, st, a);
+    return CLLM_OK;
+}
+// k_gemv_b32's CHAIN forms by type: 1 always (Q5_0 / Q5_1), 0 never (MXFP4), -1 both, the caller's `chain` picks (IQ4_NL)
+constexpr int b32_chain_forms(int T) { return T == CLLM_TYPE_MXFP4 ? 0 : T == CLLM_TYPE_IQ4_NL ? -1 : 1; }
 static void kq_launch(hipStream_t st, int wtype, const kq_args & a, dim3 grid, bool chain) {
-#define GO(T) do { if (a.ncols == 1) hipLaunchKernelGGL((k_gemv_kq<T, 1>), grid, dim3(256), 0, st, a); \
-                   else if (a.ncols <= 4) hipLaunchKernelGGL((k_gemv_kq<T, 4>), grid, dim3(256), 0, st, a); \
-                   else hipLaunchKernelGGL((k_gemv_kq<T, 8>), grid, dim3(256), 0, st, a); } while (0)
-#define GB(T, CH) do { if (a.ncols == 1) hipLaunchKernelGGL((k_gemv_b32<T, 1, CH>), grid, dim3(256), 0, st, a); \
-                       else if (a.ncols <= 4) hipLaunchKernelGGL((k_gemv_b32<T, 4, CH>), grid, dim3(256), 0, st, a); \
-                       else hipLaunchKernelGGL((k_gemv_b32<T, 8, CH>), grid, dim3(256), 0, st, a); } while (0)
-    switch (wtype) {
-        case CLLM_TYPE_Q5_K: GO(CLLM_TYPE_Q5_K); break;
-        case CLLM_TYPE_Q6_K: GO(CLLM_TYPE_Q6_K); break;
-        case CLLM_TYPE_Q2_K: GO(CLLM_TYPE_Q2_K); break;
-        case CLLM_TYPE_Q3_K: GO(CLLM_TYPE_Q3_K); break;
-        case CLLM_TYPE_IQ4_XS: GO(CLLM_TYPE_IQ4_XS); break;
-        case CLLM_TYPE_TQ1_0: GO(CLLM_TYPE_TQ1_0); break;
-        case CLLM_TYPE_TQ2_0: GO(CLLM_TYPE_TQ2_0); break;
-        case CLLM_TYPE_IQ2_XXS: GO(CLLM_TYPE_IQ2_XXS); break;
-        case CLLM_TYPE_IQ2_XS: GO(CLLM_TYPE_IQ2_XS); break;
-        case CLLM_TYPE_IQ2_S: GO(CLLM_TYPE_IQ2_S); break;
-        case CLLM_TYPE_IQ3_XXS: GO(CLLM_TYPE_IQ3_XXS); break;
-        case CLLM_TYPE_IQ3_S: GO(CLLM_TYPE_IQ3_S); break;
-        case CLLM_TYPE_IQ1_S: GO(CLLM_TYPE_IQ1_S); break;
-        case CLLM_TYPE_IQ1_M: GO(CLLM_TYPE_IQ1_M); break;
-        case CLLM_TYPE_Q5_0: GB(CLLM_TYPE_Q5_0, true); break;
-        case CLLM_TYPE_Q5_1: GB(CLLM_TYPE_Q5_1, true); break;
-        case CLLM_TYPE_IQ4_NL: if (chain) GB(CLLM_TYPE_IQ4_NL, true); else GB(CLLM_TYPE_IQ4_NL, false); break;
-        default: GB(CLLM_TYPE_MXFP4, false); break;
-    }
-#undef GO
-#undef GB
+    (void) with_kq_type(wtype, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value, CH = b32_chain_forms(T);
+        if constexpr (wt::of(T).family == wt::kq256) return kq_launch_nc(st, a, grid, k_gemv_kq<T, 1>, k_gemv_kq<T, 4>, k_gemv_kq<T, 8>);
+        else if constexpr (CH >= 0) return kq_launch_nc(st, a, grid, k_gemv_b32<T, 1, CH == 1>, k_gemv_b32<T, 4, CH == 1>, k_gemv_b32<T, 8, CH == 1>);
+        else return chain ? kq_launch_nc(st, a, grid, k_gemv_b32<T, 1, true>, k_gemv_b32<T, 4, true>, k_gemv_b32<T, 8, true>)
+                          : kq_launch_nc(st, a, grid, k_gemv_b32<T, 1, false>, k_gemv_b32<T, 4, false>, k_gemv_b32<T, 8, false>);
+    });
 }
 int launch_gemv_kq(hipStream_t st, int wtype, const tview & w, const void * act, size_t act_stride, int64_t M, float * dst, int64_t ldd) {
     const int64_t K = w.ne[0], N = w.ne[1];
     if (kq_check(wtype, w, K, N)) return CLLM_E_UNSUPPORTED;
     const int kind = act_kind_of(wtype);
     kq_args a = {};
-    a.W = w.data; a.nb01 = w.nb[1]; a.N = (int) N; a.nblk = (int)(K / (is_k256_type(wtype) ? 256 : 32));
+    a.W = w.data; a.nb01 = w.nb[1]; a.N = (int) N; a.nblk = (int)(K / wtype_blck(wtype));
     a.act_stride = (int64_t) act_stride; a.off_d = (int) act_off_d(K); a.off_s = (int) act_off_s(K, kind);
     a.ldd = ldd;
     const dim3 grid((unsigned)((N * 8 + 255) / 256));
@@ -394,7 +382,7 @@ int launch_gemv_kq_id(hipStream_t st, int wtype, const tview & as, const void * 
     if (kq_check(wtype, as, K, N) || n_used * n_tok > 65535 || n_used <= 0 || ids.nb[0] != 4 || ids.nb[1] % 4 || dst.nb[1] % 4 || dst.nb[2] % 4) return CLLM_E_UNSUPPORTED;
     const int kind = act_kind_of(wtype);
     kq_args a = {};
-    a.W = as.data; a.nb01 = as.nb[1]; a.N = (int) N; a.nblk = (int)(K / (is_k256_type(wtype) ? 256 : 32));
+    a.W = as.data; a.nb01 = as.nb[1]; a.N = (int) N; a.nblk = (int)(K / wtype_blck(wtype));
     a.act = (const char *) act; a.act_stride = (int64_t) act_stride; a.off_d = (int) act_off_d(K); a.off_s = (int) act_off_s(K, kind);
     a.dst = (float *) dst.data; a.ldd = (int64_t)(dst.nb[1] / 4); a.ncols = 1;
     a.ids = (const int32_t *) ids.data; a.ids_nb1 = (int64_t)(ids.nb[1] / 4); a.nb02 = as.nb[2]; a.dst_tok = (int64_t)(dst.nb[2] / 4); a.n_used = (int) n_used; a.ne11 = (int) ne11;

@@ -13,7 +13,7 @@ int launch_moe_router(hipStream_t st, int wtype, const void * W, int64_t K, int6
     gemv_dec_args a;
     a.px = px; a.pw = pw; a.W = (const char *) W; a.eps = eps; a.dst = probs;
     a.xnorm_out(xnorm); a.topk_out(ids); a.topk_k(k);
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         return p.npre == 1 ? gemv_dec_launch<FMT, 1, 2, 1>(st, p, a) : gemv_dec_launch<FMT, 1, 2, 4>(st, p, a);
     });
@@ -30,7 +30,7 @@ int launch_gemv_decode_id_combine(hipStream_t st, int wtype, const void * W, siz
     gemv_dec_args a;
     a.px = px; a.W = (const char *) W; a.dst = dst; a.resid = resid; a.w_expert_bytes = w_expert_bytes;
     a.moe_ids(ids); a.moe_probs(probs); a.act_slot_stride(px_slot_stride);
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         return p.npre == 1 ? gemv_dec_launch<FMT, 2, 3, 1>(st, p, a) : p.npre == 4 ? gemv_dec_launch<FMT, 2, 3, 4>(st, p, a) : gemv_dec_launch<FMT, 2, 3, 8>(st, p, a);
     });
@@ -48,7 +48,7 @@ int launch_gemv_decode_id_router_silu(hipStream_t st, int wtype, const void * W,
     gemv_dec_args a;
     a.px = px; a.pw = pw; a.W = (const char *) W; a.eps = eps; a.dst = dst; a.w_expert_bytes = w_expert_bytes;
     a.router_w(Wr); a.n_experts(ne); a.probs_out(probs); a.topk_out(ids); a.out_slot_stride(dst_slot_stride);
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         return p.npre == 1 ? gemv_dec_launch<FMT, 1, 5, 1, true>(st, p, a) : gemv_dec_launch<FMT, 1, 5, 4, true>(st, p, a);
     });

@@ -17,7 +17,7 @@
 
 // false: CLLM_E_UNSUPPORTED.  What is a kernel's own stays with its launcher: rows per wave or team, nblk %, grid caps, W's alignment, k_gemv_team32's K >= 256
 static inline bool gemv_row_shape_ok(int wtype, int64_t K, int64_t nrows, int pro, int epi, const float * bias, const float * resid) {
-    if (!is_quant_type(wtype) || K % (wtype == CLLM_TYPE_Q4_K ? 256 : 32) || pro < 1 || pro > 4 || nrows <= 0 || K > gemv_k_max(pro)) return false;
+    if (!is_quant_type(wtype) || K % wtype_blck(wtype) || pro < 1 || pro > 4 || nrows <= 0 || K > gemv_k_max(pro)) return false;
     const uint64_t row_bytes = cllm_row_size(wtype, K);
     if (row_bytes % 4 || (uint64_t) nrows * row_bytes >= (1ull << 32)) return false;      // rows are whole dwords; byte offsets into the matrix are 32-bit
     if (epi == 1 && (pro != 1 || bias || resid)) return false;                            // SiLU(gate) * up: behind the norm prologue only, nothing added
@@ -25,7 +25,7 @@ static inline bool gemv_row_shape_ok(int wtype, int64_t K, int64_t nrows, int pr
 }
 
 static inline size_t gemv_row_lds(int wtype, int64_t K, bool c0_plane, size_t staged) {
-    return act_row_bytes(K, wtype == CLLM_TYPE_Q4_K ? ACT_Q8_K : wtype == CLLM_TYPE_Q4_1 ? ACT_Q8_1 : ACT_Q8_0) + (c0_plane ? (size_t) K : 0) + staged;
+    return act_row_bytes(K, act_kind_of(wtype)) + (c0_plane ? (size_t) K : 0) + staged;
 }
 
 template <auto KERNEL, int MAX_DYN_LDS, class... Args>
@@ -39,10 +39,10 @@ static int gemv_row_launch(hipStream_t st, int grid, size_t lds, Args... args) {
 
 template <int N> using gemv_c = std::integral_constant<int, N>;
 
-// leaf(gemv_c<FMT>) for the three 32-weight block formats (the launcher has refused every other type)
+// leaf(gemv_c<FMT>) for the three tuned 32-weight block formats (the launcher has refused every other type)
 template <class Leaf>
 static int gemv_row_by_type32(int wtype, Leaf && leaf) {
-    return wtype == CLLM_TYPE_Q4_0 ? leaf(gemv_c<CLLM_TYPE_Q4_0>()) : wtype == CLLM_TYPE_Q4_1 ? leaf(gemv_c<CLLM_TYPE_Q4_1>()) : leaf(gemv_c<CLLM_TYPE_Q8_0>());
+    return with_tuned_type(wtype, [&](auto t) -> int { if constexpr (wtype_blck(decltype(t)::value) == 32) return leaf(t); else return CLLM_E_UNSUPPORTED; });
 }
 
 // leaf(gemv_c<PRO>, gemv_c<NPRE>) for the pairs the prologue has (NPRE 8: the plain-quantize forms only, common.h gemv_k_max); the leaf names its kernel's instantiations

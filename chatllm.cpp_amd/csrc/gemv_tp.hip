@@ -24,7 +24,7 @@ int launch_gemv_decode_tp_scatter(hipStream_t st, int wtype, const void * W, int
     gemv_dec_args a;
     a.px = px; a.W = (const char *) W;
     a.tp_ctx(ctx_dev); a.tp_site_out(site);
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         const int npre = p.npre;
         if (pro == 2) return npre == 1 ? gemv_dec_launch<FMT, 2, 4, 1>(st, p, a) : npre == 4 ? gemv_dec_launch<FMT, 2, 4, 4>(st, p, a) : gemv_dec_launch<FMT, 2, 4, 8>(st, p, a);
@@ -42,7 +42,7 @@ int launch_gemv_decode_tp_gather(hipStream_t st, int wtype, const void * W, int6
     gemv_dec_args a;
     a.px = px; a.pw = pw; a.W = (const char *) W; a.eps = eps; a.dst = dst; a.xout = xout; a.bias = bias; a.ts = g_tp_ts;
     a.tp_ctx(ctx_dev); a.tp_site_in(site);
-    return gemv_dec_by_type(wtype, [&](auto fmt) {
+    return with_tuned_type(wtype, [&](auto fmt) {
         constexpr int FMT = decltype(fmt)::value;
         const int npre = p.npre;
         if (epi == 1) return npre == 1 ? gemv_dec_launch<FMT, 5, 1, 1>(st, p, a) : gemv_dec_launch<FMT, 5, 1, 4>(st, p, a);

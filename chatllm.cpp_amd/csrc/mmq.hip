@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
 
     // ---- staging is split in two: global -> registers (issued one K step ahead, so the loads fly during the MFMA work of the
     //      current step) and registers -> LDS (unpack + store, between the two barriers of a step) ----
-    constexpr int BS = TYPE == CLLM_TYPE_Q8_0 ? 34 : IS_41 ? 20 : 18, QOFF = IS_41 ? 4 : 2;      // block bytes, offset of the quants
+    constexpr int BS = (int) wtype_size(TYPE), QOFF = IS_41 ? 4 : 2;      // block bytes, offset of the quants
     struct __attribute__((packed, aligned(2))) q16 { uint32_t x, y, z, w; };
     constexpr int NXA = MMQ_BM * 16 / NT;                          // activation chunk tasks per thread
     constexpr int NXS = IS_K ? (MMQ_BM * 9 + NT - 1) / NT : MMQ_BM * (IS_41 ? 16 : 8) / NT;      // activation scale tasks per thread
@@ -347,18 +347,15 @@ int launch_mmq(hipStream_t st, int wtype, const tview & w, const void * act, siz
     a.dst = (float *) d.data; a.ldd = d.nb[1] / 4; a.resid = resid; a.ldr = ldr; a.epi = epi;
     if (epi && (epi != 1 || resid || a.N % 2)) FAIL(CLLM_E_INVALID, "mmq: epilogue %d", epi);
 
-#define GO(T) do { static uint64_t attr = 0; \
-        constexpr int BM = (mmq_traits<T>::NW / 2) * 16 * mmq_traits<T>::MI, LDS = lds_total(BM, T == CLLM_TYPE_Q4_1); \
-        if (((a.M + BM - 1) / BM) * ((a.N + MMQ_BN - 1) / MMQ_BN) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "mmq: too many tiles"); \
-        const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + MMQ_BN - 1) / MMQ_BN))); \
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmq<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); } \
-        hipLaunchKernelGGL(k_mmq<T>, grid, dim3(mmq_traits<T>::NW * 64), LDS, st, a); } while (0)
-    if (wtype == CLLM_TYPE_Q4_K) GO(CLLM_TYPE_Q4_K);
-    else if (wtype == CLLM_TYPE_Q4_0) GO(CLLM_TYPE_Q4_0);
-    else if (wtype == CLLM_TYPE_Q8_0) GO(CLLM_TYPE_Q8_0);
-    else if (wtype == CLLM_TYPE_Q4_1) GO(CLLM_TYPE_Q4_1);
-    else return CLLM_E_UNSUPPORTED;
-#undef GO
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    return with_tuned_type(wtype, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
+        static uint64_t attr = 0;
+        constexpr int BM = (mmq_traits<T>::NW / 2) * 16 * mmq_traits<T>::MI, LDS = lds_total(BM, T == CLLM_TYPE_Q4_1);
+        if (((a.M + BM - 1) / BM) * ((a.N + MMQ_BN - 1) / MMQ_BN) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "mmq: too many tiles");
+        const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + MMQ_BN - 1) / MMQ_BN)));
+        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmq<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
+        hipLaunchKernelGGL(k_mmq<T>, grid, dim3(mmq_traits<T>::NW * 64), LDS, st, a);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    });
 }

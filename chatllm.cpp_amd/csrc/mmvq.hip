@@ -303,13 +303,14 @@ static int launch_one(hipStream_t st, KernelT kern, size_t lds_bytes, size_t cha
 
 static int mmvq_dispatch(hipStream_t st, int wtype, int nc, size_t lds, const mmvq_args & a, int grid_y) {
     const size_t chain = (size_t) nc * (wtype == CLLM_TYPE_Q4_K ? Q4K_CHAIN_BYTES : Q32_CHAIN_BYTES);
+    if (!is_quant_type(wtype)) FAIL(CLLM_E_UNSUPPORTED, "mmvq: weight type %d", wtype);
+    return with_tuned_type(wtype, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
 #define GO(...) return launch_one(st, __VA_ARGS__, lds, chain, a, grid_y)
-    if (wtype == CLLM_TYPE_Q4_K)      { if (nc == 4) GO(k_mmvq_q4_K<4, 1>); else if (nc == 2) GO(k_mmvq_q4_K<2, 1>); else GO(k_mmvq_q4_K<1, 1>); }
-    else if (wtype == CLLM_TYPE_Q8_0) { if (nc == 4) GO(k_mmvq_q32<4, CLLM_TYPE_Q8_0>); else if (nc == 2) GO(k_mmvq_q32<2, CLLM_TYPE_Q8_0>); else GO(k_mmvq_q32<1, CLLM_TYPE_Q8_0>); }
-    else if (wtype == CLLM_TYPE_Q4_0) { if (nc == 4) GO(k_mmvq_q32<4, CLLM_TYPE_Q4_0>); else if (nc == 2) GO(k_mmvq_q32<2, CLLM_TYPE_Q4_0>); else GO(k_mmvq_q32<1, CLLM_TYPE_Q4_0>); }
-    else if (wtype == CLLM_TYPE_Q4_1) { if (nc == 4) GO(k_mmvq_q32<4, CLLM_TYPE_Q4_1>); else if (nc == 2) GO(k_mmvq_q32<2, CLLM_TYPE_Q4_1>); else GO(k_mmvq_q32<1, CLLM_TYPE_Q4_1>); }
+        if constexpr (T == CLLM_TYPE_Q4_K) { if (nc == 4) GO(k_mmvq_q4_K<4, 1>); else if (nc == 2) GO(k_mmvq_q4_K<2, 1>); else GO(k_mmvq_q4_K<1, 1>); }
+        else                               { if (nc == 4) GO(k_mmvq_q32<4, T>);  else if (nc == 2) GO(k_mmvq_q32<2, T>);  else GO(k_mmvq_q32<1, T>); }
 #undef GO
-    FAIL(CLLM_E_UNSUPPORTED, "mmvq: weight type %d", wtype);
+    });
 }
 
 // w: [K, nrows] quant rows (dims 2,3 handled by the caller), act: ncols rows of act layout, dst: column c at dst.data + c*nb1

@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
         }
 
     // ---- staging: global -> registers (one K step ahead), registers -> LDS (unpack to fp16) ----
-    constexpr int BS = IS_Q8 ? 34 : IS_41 ? 20 : 18, QOFF = IS_41 ? 4 : 2;
+    constexpr int BS = (int) wtype_size(TYPE), QOFF = IS_41 ? 4 : 2;
     struct __attribute__((packed, aligned(2))) q16 { uint32_t x, y, z, w; };
     constexpr int CPR = KS / 16;                                    // 16-byte chunks of int8 per token and stage
     constexpr int NXA = BM * CPR / NT;                              // activation tasks per thread: (token, 16 int8)
@@ -421,24 +421,21 @@ int launch_mmx(hipStream_t st, int wtype, const tview & w, const void * act, siz
     a.act = (const char *) act; a.act_stride = act_stride; a.M = x.ne[1];
     a.dst = (float *) d.data; a.ldd = d.nb[1] / 4; a.resid = resid; a.ldr = ldr; a.epi = epi;
     if (epi && (epi != 1 || resid || a.N % 2)) FAIL(CLLM_E_INVALID, "mmx: epilogue %d", epi);
-#define GO(T) do { static uint64_t attr = 0; \
-        using TR = mmx_traits<T>; constexpr int BN = TR::WN * TR::NJ * 16, BM = TR::WM * TR::MI * 16, LDS = mmx_lds<T>(); \
-        if (((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "mmx: too many tiles"); \
-        const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN))); \
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmx<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); } \
-        hipLaunchKernelGGL(k_mmx<T>, grid, dim3(256), LDS, st, a); } while (0)
     static const bool dbg = opt_is_set(OPT_CLLM_DEBUG);
     if (dbg) {
         int nb = 0;
         (void) hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *) k_mmx<CLLM_TYPE_Q4_0>, 256, mmx_lds<CLLM_TYPE_Q4_0>());
         fprintf(stderr, "[cllm] mmx: occupancy query: %d workgroups of 256 threads per CU (Q4_0 form, %d bytes of LDS)\n", nb, mmx_lds<CLLM_TYPE_Q4_0>());
     }
-    if (wtype == CLLM_TYPE_Q4_K) GO(CLLM_TYPE_Q4_K);
-    else if (wtype == CLLM_TYPE_Q4_0) GO(CLLM_TYPE_Q4_0);
-    else if (wtype == CLLM_TYPE_Q8_0) GO(CLLM_TYPE_Q8_0);
-    else if (wtype == CLLM_TYPE_Q4_1) GO(CLLM_TYPE_Q4_1);
-    else return CLLM_E_UNSUPPORTED;
-#undef GO
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    return with_tuned_type(wtype, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
+        static uint64_t attr = 0;
+        using TR = mmx_traits<T>; constexpr int BN = TR::WN * TR::NJ * 16, BM = TR::WM * TR::MI * 16, LDS = mmx_lds<T>();
+        if (((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "mmx: too many tiles");
+        const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)));
+        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmx<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
+        hipLaunchKernelGGL(k_mmx<T>, grid, dim3(256), LDS, st, a);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    });
 }

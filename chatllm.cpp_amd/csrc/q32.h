@@ -11,7 +11,7 @@ struct __attribute__((packed, aligned(4))) u32x4_u4 { uint32_t x, y, z, w; };
 
 template <int FMT> struct q32_fmt {
     static constexpr bool IS_Q8 = FMT == CLLM_TYPE_Q8_0, IS_Q41 = FMT == CLLM_TYPE_Q4_1;
-    static constexpr int  BS = IS_Q8 ? 34 : IS_Q41 ? 20 : 18;          // bytes per block
+    static constexpr int  BS = (int) wtype_size(FMT);                  // bytes per block (types.def)
 };
 
 // One block's bytes -> registers, in two halves so that a kernel can issue the loads early and unpack when the data is needed.

@@ -20,8 +20,8 @@ __global__ void __launch_bounds__(256) k_quantize_b32(const float * __restrict__
     float v[32];
 #pragma unroll
     for (int i = 0; i < 8; i++) { const f32x4 t = *(const f32x4 *)(x + b * 32 + 4 * i); v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w; }
-    constexpr bool SIGNED = TYPE == CLLM_TYPE_Q4_0 || TYPE == CLLM_TYPE_Q5_0 || TYPE == CLLM_TYPE_Q8_0;
-    constexpr int BS = TYPE == CLLM_TYPE_Q8_0 ? 34 : TYPE == CLLM_TYPE_Q4_0 ? 18 : TYPE == CLLM_TYPE_Q4_1 ? 20 : TYPE == CLLM_TYPE_Q5_0 ? 22 : 24;
+    constexpr bool SIGNED = act_kind_of(TYPE) == ACT_Q8_0;       // no minimum in the block: the formats whose dot product reads no activation sums (Q4_0 / Q5_0 / Q8_0)
+    constexpr int BS = (int) wtype_size(TYPE);
     uint8_t out[36];
     float d, mn = 0.0f;
     if (SIGNED) {

@@ -332,12 +332,12 @@ fuse_plan make_plan(ggml_cgraph * g) {
     auto pf_ok = [&](const ggml_tensor * mm) {
         if (mm->op != GGML_OP_MUL_MAT) return false;
         const ggml_tensor * w = mm->src[0], * x = mm->src[1];
-        const uintptr_t wal = w->type == GGML_TYPE_Q4_K ? 15 : w->type == GGML_TYPE_Q4_1 ? 3 : 1;
+        const uintptr_t wal = (uintptr_t) wtype_row_align((int) w->type) - 1;       // csrc/types.def: what cllm_op_mul_mat_ex demands of the rows
         return is_q(w->type) && w->ne[2] == 1 && w->ne[3] == 1 && w->nb[1] == ggml_row_size(w->type, w->ne[0]) && !((uintptr_t) w->data & wal) && !(w->nb[1] & wal) &&
                x->type == GGML_TYPE_F32 && x->ne[2] == 1 && x->ne[3] == 1 && x->ne[1] >= pf_min && x->ne[1] <= 65535 && x->nb[0] == 4 && x->nb[1] % 16 == 0 && !((uintptr_t) x->data & 15) &&
                mm->type == GGML_TYPE_F32 && mm->nb[0] == 4 && mm->nb[1] % 4 == 0 && mm->ne[2] == 1 && mm->ne[3] == 1;
     };
-    auto act_class = [](ggml_type t) { return t == GGML_TYPE_Q4_K ? 0 : t == GGML_TYPE_Q4_1 ? 1 : 2; };
+    auto act_class = [](ggml_type t) { return act_kind_of((int) t); };      // the act rows two projections can share (every user passed pf_ok: tuned types)
     auto uses_wdata = [](const ggml_tensor * t) { return t->op == GGML_OP_MUL_MAT || t->op == GGML_OP_MUL_MAT_ID || t->op == GGML_OP_FLASH_ATTN_EXT; };
     if (!no_pf) for (int i = 0; i < n; i++) {
         ggml_tensor * t = ggml_graph_node(g, i);

@@ -13,6 +13,7 @@
 #include "ggml-impl.h"          // ggml_node_get_use_count: the graph-wide use counts the fusion pass relies on
 
 #include "../../include/chatllm_hip.h"
+#include "../csrc/types.h"       // what a tensor type is: is_quant_type, is_kq_type (csrc/types.def)
 
 #include <atomic>
 #include <chrono>
@@ -107,12 +108,10 @@ size_t al256(size_t b) { return (b + 255) & ~(size_t) 255; }
 // t seen as a dense F32 vector of K elements / as a dense F32 matrix of ne1 rows of ne0 elements
 cllm_tensor as_vec(cllm_tensor t, int64_t K) { t.ne[0] = K; t.ne[1] = t.ne[2] = t.ne[3] = 1; t.nb[1] = t.nb[2] = t.nb[3] = (size_t) K * 4; return t; }
 cllm_tensor as_mat(cllm_tensor t, int64_t ne0, int64_t ne1) { t.ne[0] = ne0; t.ne[1] = ne1; t.ne[2] = t.ne[3] = 1; t.nb[1] = (size_t) ne0 * 4; t.nb[2] = t.nb[3] = t.nb[1] * (size_t) ne1; return t; }
-bool is_q(ggml_type t) { return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K; }
-// the coverage types: mat-mul and GET_ROWS only (gemv_kq.hip): no fused launch takes them
-bool is_kq(ggml_type t) {
-    return t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_MXFP4 || t == GGML_TYPE_IQ4_XS || t == GGML_TYPE_TQ1_0 || t == GGML_TYPE_TQ2_0 ||
-           t == GGML_TYPE_IQ2_XXS || t == GGML_TYPE_IQ2_XS || t == GGML_TYPE_IQ2_S || t == GGML_TYPE_IQ3_XXS || t == GGML_TYPE_IQ3_S || t == GGML_TYPE_IQ1_S || t == GGML_TYPE_IQ1_M;
-}
+// the tuned and the coverage types (csrc/types.def: ggml_type and the cllm id are the same number, as desc() relies on); the coverage types take mat-mul and GET_ROWS
+// only (gemv_kq.hip): no fused launch takes them
+bool is_q(ggml_type t) { return is_quant_type((int) t); }
+bool is_kq(ggml_type t) { return is_kq_type((int) t); }
 bool dense_rows(const ggml_tensor * t) { return t->nb[0] == ggml_type_size(t->type); }
 bool f32_dense(const ggml_tensor * t) { return t && t->type == GGML_TYPE_F32 && t->nb[0] == 4; }
 

@@ -9,6 +9,10 @@ import os
 
 import numpy as np
 
+from conftest import load_package
+
+_tensor = load_package().tensor
+
 REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
 GGML_TYPE_F32 = 0
 # the codes of cllm_unary (== enum ggml_unary_op); SQR is an op of its own (GGML_OP_SQR)
@@ -19,7 +23,7 @@ _BINARY = {"add": "ggml_add", "mul": "ggml_mul", "div": "ggml_div"}
 GGML_TYPE_I32 = 26
 GGML_TYPE_F16, GGML_TYPE_Q8_0, GGML_TYPE_I64 = 1, 8, 27
 # (bytes of a block, elements of a block) of the types the data-movement entry points take: ggml.c type_traits
-_BLOCK = {0: (4, 1), 1: (2, 1), 26: (4, 1), 27: (8, 1), 2: (18, 32), 8: (34, 32), 12: (144, 256), 14: (210, 256)}
+_BLOCK = {t: (_tensor.TYPE_SIZE[t], _tensor.BLCK[t]) for t in _tensor.TYPE_SIZE}
 
 
 class _InitParams(C.Structure):

@@ -2,9 +2,10 @@
 scale bytes so that every bit pattern of the 6-bit scale packing is exercised)"""
 import numpy as np
 
-TYPE_SIZE = {2: 18, 3: 20, 8: 34, 12: 144, 13: 176, 14: 210, 6: 22, 7: 24, 10: 84, 11: 110, 20: 18, 39: 17, 23: 136, 34: 54, 35: 66, 16: 66, 17: 74, 22: 82, 18: 98, 21: 110, 19: 50, 29: 56}
-BLCK = {2: 32, 3: 32, 8: 32, 12: 256, 13: 256, 14: 256, 6: 32, 7: 32, 10: 256, 11: 256, 20: 32, 39: 32, 23: 256, 34: 256, 35: 256, 16: 256, 17: 256, 22: 256, 18: 256, 21: 256, 19: 256, 29: 256}
+from conftest import load_package
 
+# bytes and elements per block by type id: the package's dicts (tests/test_types.py holds them against csrc/types.def)
+TYPE_SIZE, BLCK = load_package().tensor.TYPE_SIZE, load_package().tensor.BLCK
 
 def rand_blocks(t, rows, K, rng, d_scale=0.01):
     nb = K // BLCK[t]

@@ -1344,3 +1344,38 @@ def test_argmax_advance_and_set_pick_the_first_maximum(gpu, n):
                 assert tok_host.value == (want if with_host else -7), (name, n, "tok_host", tok_host.value)
     finally:
         L.cllm_host_free(host)
+
+
+# ---- the MUL_MAT route (capi.hip mm_route): the op and the helper that times "what the op launches" walk ONE list -------------------------------------------
+def _route_case(gpu, t, M, seed):
+    """Q4_0 / Q4_1 / Q8_0 / Q4_K at K = 256 (one Q4_K super-block), N = 64 (one mmx tile): dst of cllm_op_mul_mat, dst of cllm_bench_mul_mat_kernel (iters 1), the oracle's"""
+    K, N = 256, 64
+    L = gpu.lib.get()
+    r = np.random.default_rng(seed)
+    w = rand_blocks(t, N, K, r)
+    x = r.standard_normal((M, K)).astype(np.float32)
+    want = np.zeros((M, N), np.float32)
+    O.mul_mat(O.tensor(w, t, [K, N]), O.tensor(x, O.F32, [K, M]), O.tensor(want, O.F32, [N, M]))
+    dw, dx = gpu.Tensor.from_numpy(w, t, [K, N]), gpu.Tensor.from_numpy(x)
+    op = gpu.ops.mul_mat(dw, dx).numpy().reshape(M, N)
+    dst = gpu.Tensor.from_numpy(np.full((M, N), np.nan, np.float32))
+    cw, cx, cd = dw.c(), dx.c(), dst.c()
+    scratch = gpu.tensor.Buffer(L.cllm_mul_mat_wsize(C.byref(cw), C.byref(cx)) + 256)
+    ptrs, us = (C.c_void_p * 1)(dw.data_ptr().value), C.c_float()
+    gpu.lib.check(L.cllm_bench_mul_mat_kernel(None, C.byref(cw), ptrs, 1, C.byref(cx), C.byref(cd), scratch.ptr, scratch.nbytes, 1, C.byref(us)), "bench_mul_mat_kernel")
+    return op, dst.numpy().reshape(M, N), want
+
+
+@pytest.mark.parametrize("t", [2, 3, 8, 12], ids=["q4_0", "q4_1", "q8_0", "q4_k"])
+def test_the_bench_helper_launches_what_mul_mat_launches(gpu, t):
+    """M 1: the decode mat-vec / mmvq; 4 | 5 and 9 | 10: both sides of the two exact_gemm_min_cols crossovers (mmvq in chunks | mmx); 33: past CLLM_MMQ_MIN_COLS.
+    Default (exact) mode: every route is in the reference's order, so op == helper == oracle bit for bit.  Fast mode at M = 33 (mmq, tolerance tier): op == helper."""
+    assert gpu.lib.get().cllm_get_prefill_mode() == 1
+    for M in (1, 4, 5, 9, 10, 33):
+        op, bench, want = _route_case(gpu, t, M, 100 * t + M)
+        assert np.array_equal(op.view(np.uint32), want.view(np.uint32)), M
+        assert np.array_equal(bench.view(np.uint32), op.view(np.uint32)), M
+    with prefill_mode(gpu, 0):
+        op, bench, _ = _route_case(gpu, t, 33, 100 * t + 34)
+        assert np.array_equal(bench.view(np.uint32), op.view(np.uint32))
+    assert gpu.lib.get().cllm_get_prefill_mode() == 1
