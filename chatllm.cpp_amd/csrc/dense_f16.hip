@@ -14,42 +14,22 @@
 // stage is written while the current one feeds the matrix cores), global -> registers one stage ahead (raw bytes: nothing converted before the data is
 // needed), 144-byte tile rows (conflict-free ds_read_b128 fragments).  A wave owns 2 x 2 or 4 x 4 MFMA tiles (accumulators in AGPRs).  A operand = tokens, B operand = weight rows:
 // D[v] = (token (v & 3) + 8 (v >> 2) + 4 (lane >> 5), row lane & 31): stores are 128-byte runs.
-#include "common.h"
+#include "mm_tile.h"
 
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-struct mmd_args {
-    const char * W; int64_t nb01; int64_t N; int64_t K;
-    const uint16_t * X; int64_t ldx; int64_t M;      // fp16 activations [M][ldx]
-    float * dst; int64_t ldd;
-    const float * resid; int64_t ldr; int epi;
-};
 #define MMD_KS 64
 #define MMD_LD (MMD_KS * 2 + 16)
-
-__device__ __forceinline__ void b2h(uint32_t u, uint32_t & lo, uint32_t & hi) {       // four unsigned bytes -> fp16 pairs 1024 + byte (0x64uu)
-    lo = __builtin_amdgcn_perm(0x64646464u, u, 0x04010400u);
-    hi = __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u);
-}
-__device__ __forceinline__ uint32_t h2op_sub(uint32_t x, uint32_t c) { const h2v r = __builtin_bit_cast(h2v, x) - __builtin_bit_cast(h2v, c); return __builtin_bit_cast(uint32_t, r); }
-__device__ __forceinline__ uint32_t h2op_mul(uint32_t x, uint32_t c) { const h2v r = __builtin_bit_cast(h2v, x) * __builtin_bit_cast(h2v, c); return __builtin_bit_cast(uint32_t, r); }
-__device__ __forceinline__ uint32_t h2op_fma(uint32_t x, uint32_t a, uint32_t c) {
-    const h2v r = __builtin_elementwise_fma(__builtin_bit_cast(h2v, x), __builtin_bit_cast(h2v, a), __builtin_bit_cast(h2v, c));
-    return __builtin_bit_cast(uint32_t, r);
-}
-__device__ __forceinline__ uint32_t h2dup(uint16_t h) { return (uint32_t) h * 0x00010001u; }
 
 // BM tokens x BN weight rows per 256-thread workgroup; a wave owns (BM / 2) x (BN / 2) = MI x NJ MFMA tiles.  128 x 128 (2 x 2 tiles per wave, two workgroups per CU):
 // one LDS fragment read per MFMA -- the LDS pipe, not the matrix cores, is the busy unit.  256 x 256 (4 x 4 tiles per wave, one workgroup per CU): half a read per MFMA,
 // and the dequantization of a weight tile is shared by twice as many tokens.
 template <int TYPE, int BM, int BN>
-__global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd_args a) {
+__global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mm_tile_args a) {      // a.act: the fp16 activations, rows a.act_stride bytes apart; no residual, no epilogue form
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr bool IS_K = TYPE == CLLM_TYPE_Q4_K, IS_41 = TYPE == CLLM_TYPE_Q4_1, IS_Q8 = TYPE == CLLM_TYPE_Q8_0;
     constexpr int STAGE = (BN + BM) * MMD_LD, WM = BM / 2, WN = BN / 2, MI = WM / 32, NJ = WN / 32, WT = BN / 128, XT = BM / 32;
-    constexpr int BS = (int) wtype_size(TYPE), QOFF = IS_41 ? 4 : 2;
+    constexpr int BS = (int) wtype_size(TYPE);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned mt, nt;
     gemm_tile_of(blockIdx.x, (unsigned)((a.M + BM - 1) / BM), (unsigned)((a.N + BN - 1) / BN), 4, mt, nt);
@@ -66,7 +46,6 @@ __global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd
 #undef MMD_DECL
 
     // ---- staging: global -> registers (raw), registers -> LDS (dequantize) ----
-    struct __attribute__((packed, aligned(2))) q16 { uint32_t x, y, z, w; };
     const int wrow0 = tid >> 1, whalf = tid & 1;                    // weight tasks: (row wrow0 + 128 w, 32 of the stage's 64 elements)
     u32x4 rq_[WT], rq2_[WT], rh_[WT]; uint32_t rd_[WT];
     u32x4 rx[XT];
@@ -77,18 +56,8 @@ __global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd
         const int64_t n = n0 + wrow0 + 128 * w, e0 = k0 + 32 * whalf;
         rq = u32x4{0, 0, 0, 0}; rq2 = u32x4{0, 0, 0, 0}; rh = u32x4{0, 0, 0, 0}; rd = 0;
         if (n < a.N && e0 < K) {
-            if constexpr (IS_K) {
-                const char * bp = a.W + n * a.nb01 + (k0 >> 8) * 144;
-                const int c = (int)((k0 & 255) >> 6);
-                rh = *(const u32x4 *) bp;
-                rq = *(const u32x4 *)(bp + 16 + 32 * c); rq2 = *(const u32x4 *)(bp + 32 + 32 * c);
-            } else {
-                const char * bp = a.W + n * a.nb01 + (e0 >> 5) * BS;
-                if (IS_41) rd = *(const uint32_t *) bp; else rd = *(const uint16_t *) bp;
-                const q16 q0 = *(const q16 *)(bp + QOFF);
-                rq = u32x4{q0.x, q0.y, q0.z, q0.w};
-                if (IS_Q8) { const q16 q1 = *(const q16 *)(bp + 18); rq2 = u32x4{q1.x, q1.y, q1.z, q1.w}; }
-            }
+            if constexpr (IS_K) { const wchunk_q4k r = wchunk_q4k_load(a.W + n * a.nb01 + (k0 >> 8) * 144, (int)((k0 & 255) >> 6)); rh = r.h; rq = r.q; rq2 = r.q2; }
+            else { const wblock32_raw r = wblock32_load<TYPE>(a.W + n * a.nb01 + (e0 >> 5) * BS); rd = r.d; rq = r.q; rq2 = r.q2; }
         }
       }
 #pragma unroll
@@ -96,7 +65,7 @@ __global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd
             const int c = tid + 256 * t, row = c >> 3, ch = c & 7;
             const int64_t m = m0 + row, e = k0 + ch * 8;
             rx[t] = u32x4{0, 0, 0, 0};
-            if (m < a.M && e < K) rx[t] = *(const u32x4 *)(a.X + m * a.ldx + e);      // (K % 8 == 0: whole chunks)
+            if (m < a.M && e < K) rx[t] = *(const u32x4 *)(a.act + m * a.act_stride + e * 2);      // (K % 8 == 0: whole chunks)
         }
     };
     auto commit = [&](int stage, int64_t k0) {
@@ -109,41 +78,40 @@ __global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd
         if constexpr (IS_K) {
             // sub-block 2 c + whalf of the super-block: y = d * sc * nib - dmin * m (dequantize_row_q4_K), here as one fp16 fma per pair with d * sc and dmin * m rounded to fp16
             const int c = (int)((k0 & 255) >> 6), sbi = 2 * c + whalf;
-            const uint32_t u0 = rh.y & 0x3f3f3f3fu, u2 = rh.z & 0x3f3f3f3fu;
-            const uint32_t u1 = (rh.w & 0x0f0f0f0fu) | (((rh.y >> 6) & 0x03030303u) << 4);
-            const uint32_t u3 = ((rh.w >> 4) & 0x0f0f0f0fu) | (((rh.z >> 6) & 0x03030303u) << 4);
-            const float sc = (float)((((sbi & 4) ? u1 : u0) >> (8 * (sbi & 3))) & 0xff), mn = (float)((((sbi & 4) ? u3 : u2) >> (8 * (sbi & 3))) & 0xff);
+            const q4k_scales_t u = q4k_scales(rh.y, rh.z, rh.w);
+            const float sc = (float)((((sbi & 4) ? u.u1 : u.u0) >> (8 * (sbi & 3))) & 0xff), mn = (float)((((sbi & 4) ? u.u3 : u.u2) >> (8 * (sbi & 3))) & 0xff);
             const float d = h2f((uint16_t)(rh.x & 0xffff)), dmin = h2f((uint16_t)(rh.x >> 16));
-            const uint32_t d1 = h2dup(f2h(d * sc)), m1 = h2dup(f2h(-(dmin * mn))), k1024 = 0x64006400u;
-            const uint32_t q[8] = { rq.x, rq.y, rq.z, rq.w, rq2.x, rq2.y, rq2.z, rq2.w };
+            const uint32_t d1 = h2_splat16(f2h(d * sc)), m1 = h2_splat16(f2h(-(dmin * mn))), k1024 = 0x64006400u;
+            const u32x4 qa = whalf ? nib_hi(rq) : nib_lo(rq), qb = whalf ? nib_hi(rq2) : nib_lo(rq2);
+            const uint32_t q[8] = { qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w };
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 uint32_t lo, hi;
-                b2h(whalf ? (q[e] >> 4) & 0x0f0f0f0fu : q[e] & 0x0f0f0f0fu, lo, hi);
-                o[2 * e] = h2op_fma(h2op_sub(lo, k1024), d1, m1); o[2 * e + 1] = h2op_fma(h2op_sub(hi, k1024), d1, m1);
+                bytes_to_h1024(q[e], lo, hi);
+                o[2 * e] = h2_fma(h2_sub(lo, k1024), d1, m1); o[2 * e + 1] = h2_fma(h2_sub(hi, k1024), d1, m1);
             }
         } else if constexpr (IS_Q8) {
-            const uint32_t dd = h2dup((uint16_t) rd);
+            const uint32_t dd = h2_splat16((uint16_t) rd);
             const uint32_t q[8] = { rq.x, rq.y, rq.z, rq.w, rq2.x, rq2.y, rq2.z, rq2.w };
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 uint32_t lo, hi;
-                b2h(q[e] ^ 0x80808080u, lo, hi);
-                o[2 * e] = h2op_mul(h2op_sub(lo, 0x64806480u), dd); o[2 * e + 1] = h2op_mul(h2op_sub(hi, 0x64806480u), dd);
+                bytes_to_h1024(q[e] ^ 0x80808080u, lo, hi);
+                o[2 * e] = h2_mul(h2_sub(lo, 0x64806480u), dd); o[2 * e + 1] = h2_mul(h2_sub(hi, 0x64806480u), dd);
             }
         } else {
-            const uint32_t dd = h2dup((uint16_t)(rd & 0xffff)), mm = h2dup((uint16_t)(rd >> 16));
-            const uint32_t q[4] = { rq.x, rq.y, rq.z, rq.w };
+            const uint32_t dd = h2_splat16((uint16_t)(rd & 0xffff)), mm = h2_splat16((uint16_t)(rd >> 16));
+            const u32x4 ql = nib_lo(rq), qh = nib_hi(rq);
 #pragma unroll
             for (int e = 0; e < 4; e++) {                               // elements 4 e .. (low nibbles), 16 + 4 e .. (high nibbles)
                 uint32_t lo, hi, lo2, hi2;
-                b2h(q[e] & 0x0f0f0f0fu, lo, hi); b2h((q[e] >> 4) & 0x0f0f0f0fu, lo2, hi2);
+                bytes_to_h1024(ql[e], lo, hi); bytes_to_h1024(qh[e], lo2, hi2);
                 if (IS_41) {
-                    o[2 * e] = h2op_fma(h2op_sub(lo, 0x64006400u), dd, mm); o[2 * e + 1] = h2op_fma(h2op_sub(hi, 0x64006400u), dd, mm);
-                    o[8 + 2 * e] = h2op_fma(h2op_sub(lo2, 0x64006400u), dd, mm); o[8 + 2 * e + 1] = h2op_fma(h2op_sub(hi2, 0x64006400u), dd, mm);
+                    o[2 * e] = h2_fma(h2_sub(lo, 0x64006400u), dd, mm); o[2 * e + 1] = h2_fma(h2_sub(hi, 0x64006400u), dd, mm);
+                    o[8 + 2 * e] = h2_fma(h2_sub(lo2, 0x64006400u), dd, mm); o[8 + 2 * e + 1] = h2_fma(h2_sub(hi2, 0x64006400u), dd, mm);
                 } else {
-                    o[2 * e] = h2op_mul(h2op_sub(lo, 0x64086408u), dd); o[2 * e + 1] = h2op_mul(h2op_sub(hi, 0x64086408u), dd);
-                    o[8 + 2 * e] = h2op_mul(h2op_sub(lo2, 0x64086408u), dd); o[8 + 2 * e + 1] = h2op_mul(h2op_sub(hi2, 0x64086408u), dd);
+                    o[2 * e] = h2_mul(h2_sub(lo, 0x64086408u), dd); o[2 * e + 1] = h2_mul(h2_sub(hi, 0x64086408u), dd);
+                    o[8 + 2 * e] = h2_mul(h2_sub(lo2, 0x64086408u), dd); o[8 + 2 * e + 1] = h2_mul(h2_sub(hi2, 0x64086408u), dd);
                 }
             }
         }
@@ -184,27 +152,11 @@ __global__ void __launch_bounds__(256, (BM + BN) <= 256 ? 2 : 1) k_mmd(const mmd
         stage ^= 1;
     }
 
-    const int64_t nv = (a.N / 2) & ~(int64_t) 7;
+    const mm_tile_store<MM_STORE_PLAIN> st(a, lane);
     auto store_tile = [&](int i, int j, const f32x16 & c) {
         const int64_t n = n0 + wn + j * 32 + l31;
-        if (a.epi == 1) {
-            const int64_t u = n >> 1;
-            const bool nok = !(lane & 1) && n + 1 < a.N, body = u < nv;
 #pragma unroll
-            for (int v = 0; v < 16; v++) {
-                const int64_t m = m0 + wm + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * l5;
-                const float r = c[v];
-                const float up = dpp_f<DPP_QUAD_XOR1>(r);
-                if (nok && m < a.M) a.dst[m * a.ldd + u] = silu_any(r, body) * up;
-            }
-        } else {
-#pragma unroll
-            for (int v = 0; v < 16; v++) {
-                const int64_t m = m0 + wm + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * l5;
-                const float r = c[v];
-                if (n < a.N && m < a.M) a.dst[m * a.ldd + n] = a.resid ? r + a.resid[m * a.ldr + n] : r;
-            }
-        }
+        for (int v = 0; v < 16; v++) st(m0 + wm + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * l5, n, c[v]);
     };
 #define MMD_STORE(i, j) if constexpr (i < MI && j < NJ) store_tile(i, j, c##i##j);
     MMD_TILES(MMD_STORE)
@@ -227,9 +179,9 @@ static int g_mmd_tile = -1;
 extern "C" __attribute__((visibility("default"))) void cllm_debug_set_mmd_tile(int tile) { g_mmd_tile = tile; }               // tests / tools: 0 pick, 128, 256
 
 // w: [K, N] quantized rows (2-D), x: [K, M] f32 rows (nb1 stride), d: [N, M] f32 (nb1 stride); CLLM_E_UNSUPPORTED -> the caller's other paths take it
-int launch_dense_f16(hipStream_t st, int wtype, const tview & w, const tview & x, const tview & d, const float * resid, int64_t ldr, int epi) {
+int launch_dense_f16(hipStream_t st, int wtype, const tview & w, const tview & x, const tview & d) {
     const int64_t K = w.ne[0], N = w.ne[1], M = x.ne[1];
-    if (K % 32 || d.nb[1] % 4 || x.nb[0] != 4 || (epi && (epi != 1 || resid || N % 2)) || (wtype == CLLM_TYPE_Q4_K && ((uintptr_t) w.data % 16 || w.nb[1] % 16))) return CLLM_E_UNSUPPORTED;
+    if (K % 32 || d.nb[1] % 4 || x.nb[0] != 4 || (wtype == CLLM_TYPE_Q4_K && ((uintptr_t) w.data % 16 || w.nb[1] % 16))) return CLLM_E_UNSUPPORTED;
     if (wtype == CLLM_TYPE_Q4_1 && ((uintptr_t) w.data % 4 || w.nb[1] % 4)) return CLLM_E_UNSUPPORTED;
     if (((M + 127) / 128) * ((N + 127) / 128) > 0x7fffffff) return CLLM_E_UNSUPPORTED;
     const int64_t ldx = (K + 7) & ~(int64_t) 7;
@@ -238,24 +190,17 @@ int launch_dense_f16(hipStream_t st, int wtype, const tview & w, const tview & x
     if (!g_x16) return CLLM_E_HIP;
     hipLaunchKernelGGL(k_f32_to_f16, dim3((unsigned)((K / 2 + 255) / 256), (unsigned) M), dim3(256), 0, st, (const char *) x.data, x.nb[1], K, (uint16_t *) g_x16, ldx);
     LAUNCH_CHECK();
-    mmd_args a;
-    a.W = w.data; a.nb01 = w.nb[1]; a.N = N; a.K = K; a.X = (const uint16_t *) g_x16; a.ldx = ldx; a.M = M;
-    a.dst = (float *) d.data; a.ldd = d.nb[1] / 4; a.resid = resid; a.ldr = ldr; a.epi = epi;
+    mm_tile_args a;
+    const int rc = mm_tile_args_of(a, "mmd", w, g_x16, (size_t) ldx * 2, M, d, nullptr, 0, 0);
+    if (rc) return rc;
     // the tile: 128 x 128.  256 x 256 (CLLM_MMD_TILE=256 / cllm_debug_set_mmd_tile) is faster per GEMM in isolation where its workgroups fill the CUs evenly
     // (o 254 -> 236 us, down 861 -> 786 us at 4096 tokens) but not in the running prefill: cfg3 113.8 ms with 128 x 128, 114.0 picked per shape, 117.5 ms with
     // 256 x 256 everywhere (tools/prefill_f16_tile_ab.py, one process) -- so it is not picked.
     if (g_mmd_tile < 0) g_mmd_tile = opt_int(OPT_CLLM_MMD_TILE);  // tests / tools: 128 / 256 force
-    const int64_t big_tiles = ((M + 255) / 256) * ((N + 255) / 256);
     const bool big = g_mmd_tile == 256;
     return with_tuned_type(wtype, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
-        if (big) { constexpr int LDS = 2 * 512 * MMD_LD; static uint64_t attr = 0;
-            if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmd<T, 256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
-            hipLaunchKernelGGL((k_mmd<T, 256, 256>), dim3((unsigned) big_tiles), dim3(256), LDS, st, a); }
-        else { constexpr int LDS = 2 * 256 * MMD_LD; static uint64_t attr = 0;
-            if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmd<T, 128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
-            hipLaunchKernelGGL((k_mmd<T, 128, 128>), dim3((unsigned)(((M + 127) / 128) * ((N + 127) / 128))), dim3(256), LDS, st, a); }
-        LAUNCH_CHECK();
-        return CLLM_OK;
+        if (big) return mm_tile_launch<k_mmd<T, 256, 256>>((M + 255) / 256, (N + 255) / 256, 256, 2 * 512 * MMD_LD, st, a, "mmd");
+        return mm_tile_launch<k_mmd<T, 128, 128>>((M + 127) / 128, (N + 127) / 128, 256, 2 * 256 * MMD_LD, st, a, "mmd");
     });
 }

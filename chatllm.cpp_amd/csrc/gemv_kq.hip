@@ -75,9 +75,7 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
             const char * blk = wr + (int64_t) b * BS;
             const u32x4 h = *(const u32x4 *) blk;
             dw = h2f((uint16_t)(h.x & 0xffff)); dmin = h2f((uint16_t)(h.x >> 16));
-            const uint32_t u0 = h.y & 0x3f3f3f3fu, u2 = h.z & 0x3f3f3f3fu;                          // get_scale_min_k4 (ggml-quants.c:703-711)
-            const uint32_t u1 = (h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4);
-            const uint32_t u3 = ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4);
+            const q4k_scales_t u = q4k_scales(h.y, h.z, h.w);
             const uint32_t qh = *(const uint32_t *)(blk + 16 + 4 * A);
 #pragma unroll
             for (int c = 0; c < 4; c++) {
@@ -88,8 +86,8 @@ __global__ void __launch_bounds__(256) k_gemv_kq(const kq_args a) {
             }
 #pragma unroll
             for (int s = 0; s < 8; s++) {
-                sc8[s] = (int8_t)(((s < 4 ? u0 : u1) >> (8 * (s & 3))) & 0xff);
-                mn[s]  = (int)(((s < 4 ? u2 : u3) >> (8 * (s & 3))) & 0xff);
+                sc8[s] = (int8_t)(((s < 4 ? u.u0 : u.u1) >> (8 * (s & 3))) & 0xff);
+                mn[s]  = (int)(((s < 4 ? u.u2 : u.u3) >> (8 * (s & 3))) & 0xff);
             }
         } else if (TYPE == CLLM_TYPE_Q2_K || TYPE == CLLM_TYPE_Q3_K) {
             // term t = 4 n + j: plane j (bits 2j) of the 32-byte vector of the n-th 128 weights, bytes 4A..4A+3, against activations 128 n + 32 j + 4A..; its scale is the one of

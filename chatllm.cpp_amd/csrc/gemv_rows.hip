@@ -127,19 +127,17 @@ __global__ void __launch_bounds__(1024) k_gemv_rows(const float * __restrict__ p
             const float yd = actd[b];
             const int S0 = acts[b * 8 + 2 * kk], S1 = acts[b * 8 + 2 * kk + 1];
             const float d = h2f((uint16_t)(h.x & 0xffff)), dmin = h2f((uint16_t)(h.x >> 16));
-            const uint32_t u0s = h.y & 0x3f3f3f3fu, u2s = h.z & 0x3f3f3f3fu;
-            const uint32_t u1s = (h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4);
-            const uint32_t u3s = ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4);
+            const q4k_scales_t u = q4k_scales(h.y, h.z, h.w);
             int t;
-            t = __mul24((int)(u0s & 0xff), dot4(q0 & 0x0f0f0f0fu, al0, 0));
-            t += __mul24((int)((u0s >> 8) & 0xff), dot4((q0 >> 4) & 0x0f0f0f0fu, ah0, 0));
-            t += __mul24((int)((u0s >> 16) & 0xff), dot4(q1 & 0x0f0f0f0fu, al1, 0));
-            t += __mul24((int)(u0s >> 24), dot4((q1 >> 4) & 0x0f0f0f0fu, ah1, 0));
-            t += __mul24((int)(u1s & 0xff), dot4(q2 & 0x0f0f0f0fu, al2, 0));
-            t += __mul24((int)((u1s >> 8) & 0xff), dot4((q2 >> 4) & 0x0f0f0f0fu, ah2, 0));
-            t += __mul24((int)((u1s >> 16) & 0xff), dot4(q3 & 0x0f0f0f0fu, al3, 0));
-            t += __mul24((int)(u1s >> 24), dot4((q3 >> 4) & 0x0f0f0f0fu, ah3, 0));
-            const uint32_t mp = (kk >= 2 ? u3s : u2s) >> (16 * (kk & 1));
+            t = __mul24((int)(u.u0 & 0xff), dot4(q0 & 0x0f0f0f0fu, al0, 0));
+            t += __mul24((int)((u.u0 >> 8) & 0xff), dot4((q0 >> 4) & 0x0f0f0f0fu, ah0, 0));
+            t += __mul24((int)((u.u0 >> 16) & 0xff), dot4(q1 & 0x0f0f0f0fu, al1, 0));
+            t += __mul24((int)(u.u0 >> 24), dot4((q1 >> 4) & 0x0f0f0f0fu, ah1, 0));
+            t += __mul24((int)(u.u1 & 0xff), dot4(q2 & 0x0f0f0f0fu, al2, 0));
+            t += __mul24((int)((u.u1 >> 8) & 0xff), dot4((q2 >> 4) & 0x0f0f0f0fu, ah2, 0));
+            t += __mul24((int)((u.u1 >> 16) & 0xff), dot4(q3 & 0x0f0f0f0fu, al3, 0));
+            t += __mul24((int)(u.u1 >> 24), dot4((q3 >> 4) & 0x0f0f0f0fu, ah3, 0));
+            const uint32_t mp = (kk >= 2 ? u.u3 : u.u2) >> (16 * (kk & 1));
             const int pm = __mul24((int)(mp & 0xff), S0) + __mul24((int)((mp >> 8) & 0xff), S1);
             const float dd = yd * d, dm = (-yd) * dmin, x = (float) t, xm = (float) pm;
             if (GPR == 1) { acc = __builtin_fmaf(dd, x, acc); accm = __builtin_fmaf(dm, xm, accm); }

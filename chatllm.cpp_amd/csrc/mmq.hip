@@ -16,7 +16,7 @@
 //   Q4_K : acc_i += sc[n][s] * D      (v_mad_i32_i24, exact)   ; per super-block: acc_f += (d[n]*dx[m]) * acc_i - (dmin[n]*dx[m]) * sum_s m[n][s]*sx[m][s]
 //   Q4_0/Q8_0 : acc_f += float(D) * (dw[n][s] * dx[m][s])
 // blockIdx.x walks the token tiles fastest so that concurrently resident workgroups share weight tiles in L2.
-#include "common.h"
+#include "mm_tile.h"
 
 typedef int   i32x4 __attribute__((ext_vector_type(4)));
 
@@ -27,23 +27,12 @@ typedef int   i32x4 __attribute__((ext_vector_type(4)));
 
 template <int TYPE> struct mmq_traits;
 // NW waves per workgroup, laid out 2 (n) x NW/2 (m); a wave owns 64 (n) x 16 MI (m).  Q4_0 / Q8_0 with EIGHT waves of 64 x 32 over the same 128 x 128 tile
-// (four waves per SIMD, -DMMQ_NW_Q0=8) measured 136.0 ms against 132.4 ms for cfg3: the kernel is bound by the fold's VALU work AND the LDS fragment / scale
+// (four waves per SIMD, MI = 2, NW = 8) measured 136.0 ms against 132.4 ms for cfg3: the kernel is bound by the fold's VALU work AND the LDS fragment / scale
 // reads together (9 KB per 32-block step and wave), and the smaller wave tile reads 1.5 x the fragments -- more waves do not help, so four it stays
-#ifndef MMQ_NW_Q0
-#define MMQ_NW_Q0 4
-#endif
 template <> struct mmq_traits<CLLM_TYPE_Q4_K> { static constexpr int kb = 256, MI = 2, NW = 4; };
-template <> struct mmq_traits<CLLM_TYPE_Q4_0> { static constexpr int kb = 32,  MI = 16 / MMQ_NW_Q0, NW = MMQ_NW_Q0; };
-template <> struct mmq_traits<CLLM_TYPE_Q8_0> { static constexpr int kb = 32,  MI = 16 / MMQ_NW_Q0, NW = MMQ_NW_Q0; };
+template <> struct mmq_traits<CLLM_TYPE_Q4_0> { static constexpr int kb = 32,  MI = 4, NW = 4; };
+template <> struct mmq_traits<CLLM_TYPE_Q8_0> { static constexpr int kb = 32,  MI = 4, NW = 4; };
 template <> struct mmq_traits<CLLM_TYPE_Q4_1> { static constexpr int kb = 32,  MI = 2, NW = 4; };      // two more scale planes and operands per patch: 64 tokens
-
-struct mmq_args {
-    const char * W; int64_t nb01; int64_t N; int64_t K;
-    const char * act; size_t act_stride; int64_t M;
-    float * dst; int64_t ldd;     // dst[m * ldd + n]
-    const float * resid; int64_t ldr;      // optional: dst = acc + resid[m * ldr + n] (the MUL_MAT -> ADD pair; resid may be dst itself)
-    int epi;                               // 1: weight rows alternate gate_u, up_u; dst[m * ldd + u] = silu(acc[2u]) * acc[2u + 1]  (UNARY(SILU) -> MUL of BaseMLP::forward)
-};
 
 // LDS map (bytes)
 //   Wt  : MMQ_BN * MMQ_LD                    int8 weights
@@ -56,12 +45,12 @@ constexpr int lds_ws(int bm) { return LDS_XT + bm * MMQ_LD; }
 constexpr int lds_xs(int bm, bool q41) { return lds_ws(bm) + MMQ_BN * (q41 ? 16 : 8) * 4; }      // 4 KB (Q4_K uses 8+8+4+4 = 24 B per row), Q4_1: 8 KB
 constexpr int lds_total(int bm, bool q41) { return lds_xs(bm, q41) + bm * (q41 ? 16 : 9) * 4; }   // two workgroups per CU must fit 160 KB
 
-__device__ __forceinline__ uint32_t nib_minus8(uint32_t nib4) {   // four nibbles (one per byte, 0..15) -> four int8 (nib - 8)
-    return (((nib4 | 0x80808080u) - 0x08080808u) ^ 0x80808080u);
+__device__ __forceinline__ u32x4 nib_minus8(u32x4 nib) {          // nibbles (one per byte, 0..15) -> int8 (nib - 8)
+    return (((nib | 0x80808080u) - 0x08080808u) ^ 0x80808080u);
 }
 
 template <int TYPE>
-__global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::NW / 2) k_mmq(const mmq_args a) {
+__global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::NW / 2) k_mmq(const mm_tile_args a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr bool IS_K = TYPE == CLLM_TYPE_Q4_K, IS_41 = TYPE == CLLM_TYPE_Q4_1;
     constexpr int MMQ_MI = mmq_traits<TYPE>::MI, NT = mmq_traits<TYPE>::NW * 64, MMQ_BM = (mmq_traits<TYPE>::NW / 2) * 16 * MMQ_MI;
@@ -87,20 +76,14 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
 
     // ---- staging is split in two: global -> registers (issued one K step ahead, so the loads fly during the MFMA work of the
     //      current step) and registers -> LDS (unpack + store, between the two barriers of a step) ----
-    constexpr int BS = (int) wtype_size(TYPE), QOFF = IS_41 ? 4 : 2;      // block bytes, offset of the quants
-    struct __attribute__((packed, aligned(2))) q16 { uint32_t x, y, z, w; };
+    constexpr int BS = (int) wtype_size(TYPE);                     // block bytes
     constexpr int NXA = MMQ_BM * 16 / NT;                          // activation chunk tasks per thread
     constexpr int NXS = IS_K ? (MMQ_BM * 9 + NT - 1) / NT : MMQ_BM * (IS_41 ? 16 : 8) / NT;      // activation scale tasks per thread
     constexpr int NWT = IS_K ? (MMQ_BN * 9 + NT - 1) / NT : MMQ_BN * 8 / NT;      // weight tasks per thread
     u32x4 rx[NXA]; uint32_t rxs[NXS]; u32x4 rw[NWT]; u32x4 rw2[IS_K ? 1 : NWT]; float rwd[IS_K ? 1 : NWT]; float rwm[IS_41 ? NWT : 1];
     auto prefetch = [&](int64_t k0) {
 #pragma unroll
-        for (int t = 0; t < NXA; t++) {                            // activations: MMQ_BM rows x 256 int8 (16 chunks of 16 B per row)
-            const int c = tid + NT * t, row = c >> 4, ch = c & 15;
-            const int64_t m = m0 + row;
-            rx[t] = u32x4{0, 0, 0, 0};
-            if (m < a.M && k0 + ch * 16 < K) rx[t] = *(const u32x4 *)(a.act + m * a.act_stride + k0 + ch * 16);
-        }
+        for (int t = 0; t < NXA; t++) rx[t] = act_chunk_load<16>(a, m0, k0, tid + NT * t);      // activations: MMQ_BM rows x 256 int8 (16 chunks of 16 B per row)
 #pragma unroll
         for (int t = 0; t < NXS; t++) {
             const int c = tid + NT * t;
@@ -114,11 +97,7 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
                         rxs[t] = f == 0 ? *(const uint32_t *)(ar + act_d + (k0 / 256) * 4) : *(const uint32_t *)(ar + act_s + ((k0 / 32) + (f - 1)) * 4);
                     }
                 }
-            } else {                                               // dx[8][m] (Q4_1: then sx[8][m], the f32 s plane)
-                const int row = c % MMQ_BM, pl = c / MMQ_BM, sb = pl & 7;
-                const int64_t m = m0 + row;
-                if (m < a.M && k0 + sb * 32 < K) rxs[t] = *(const uint32_t *)(a.act + m * a.act_stride + (pl < 8 ? act_d : act_s) + ((k0 / 32) + sb) * 4);
-            }
+            } else rxs[t] = act_scale_load<MMQ_BM, 8>(a, m0, k0, act_d, act_s, c);      // dx[8][m] (Q4_1: then sx[8][m], the f32 s plane)
         }
 #pragma unroll
         for (int t = 0; t < NWT; t++) {
@@ -135,12 +114,10 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
                 const int64_t n = n0 + row, b = k0 / 32 + sb;
                 rwd[IS_K ? 0 : t] = 0.0f; rw2[IS_K ? 0 : t] = u32x4{0, 0, 0, 0}; if (IS_41) rwm[IS_41 ? t : 0] = 0.0f;
                 if (n < a.N && b * 32 < K) {
-                    const char * bp = a.W + n * a.nb01 + b * BS;
-                    rwd[IS_K ? 0 : t] = h2f(*(const uint16_t *) bp);
-                    if (IS_41) rwm[IS_41 ? t : 0] = h2f(*(const uint16_t *)(bp + 2));
-                    const q16 q0 = *(const q16 *)(bp + QOFF);
-                    rw[t] = u32x4{q0.x, q0.y, q0.z, q0.w};
-                    if (TYPE == CLLM_TYPE_Q8_0) { const q16 q1 = *(const q16 *)(bp + 18); rw2[IS_K ? 0 : t] = u32x4{q1.x, q1.y, q1.z, q1.w}; }
+                    const wblock32_raw r = wblock32_load<TYPE>(a.W + n * a.nb01 + b * BS);
+                    rwd[IS_K ? 0 : t] = h2f((uint16_t)(r.d & 0xffff));
+                    if (IS_41) rwm[IS_41 ? t : 0] = h2f((uint16_t)(r.d >> 16));
+                    rw[t] = r.q; rw2[IS_K ? 0 : t] = r.q2;
                 }
             }
         }
@@ -164,17 +141,15 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
                     const int row = c / 9, ch = c % 9;
                     const u32x4 v = rw[t];
                     if (ch == 0) {
-                        const uint32_t u0 = v.y & 0x3f3f3f3fu, u2 = v.z & 0x3f3f3f3fu;
-                        const uint32_t u1 = (v.w & 0x0f0f0f0fu) | (((v.y >> 6) & 0x03030303u) << 4);
-                        const uint32_t u3 = ((v.w >> 4) & 0x0f0f0f0fu) | (((v.z >> 6) & 0x03030303u) << 4);
-                        *(u32x2 *)(Ws + row * 8) = u32x2{u0, u1};                                   // sc[n][8]
-                        *(u32x2 *)(Ws + MMQ_BN * 8 + row * 8) = u32x2{u2, u3};                      // mn[n][8]
+                        const q4k_scales_t s = q4k_scales(v.y, v.z, v.w);
+                        *(u32x2 *)(Ws + row * 8) = u32x2{s.u0, s.u1};                               // sc[n][8]
+                        *(u32x2 *)(Ws + MMQ_BN * 8 + row * 8) = u32x2{s.u2, s.u3};                  // mn[n][8]
                         *(float *)(Ws + MMQ_BN * 16 + row * 4) = h2f((uint16_t)(v.x & 0xffff));     // d[n]
                         *(float *)(Ws + MMQ_BN * 20 + row * 4) = h2f((uint16_t)(v.x >> 16));        // dmin[n]
                     } else {
                         const int j = ch - 1, off = 64 * (j >> 1) + 16 * (j & 1);
-                        *(u32x4 *)(Wt + row * MMQ_LD + off)      = u32x4{v.x & 0x0f0f0f0fu, v.y & 0x0f0f0f0fu, v.z & 0x0f0f0f0fu, v.w & 0x0f0f0f0fu};
-                        *(u32x4 *)(Wt + row * MMQ_LD + off + 32) = u32x4{(v.x >> 4) & 0x0f0f0f0fu, (v.y >> 4) & 0x0f0f0f0fu, (v.z >> 4) & 0x0f0f0f0fu, (v.w >> 4) & 0x0f0f0f0fu};
+                        *(u32x4 *)(Wt + row * MMQ_LD + off)      = nib_lo(v);
+                        *(u32x4 *)(Wt + row * MMQ_LD + off + 32) = nib_hi(v);
                     }
                 }
             } else {
@@ -182,13 +157,8 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
                 const u32x4 q0 = rw[t];
                 u32x4 lo, hi;
                 if (TYPE == CLLM_TYPE_Q8_0) { lo = q0; hi = rw2[IS_K ? 0 : t]; }
-                else if (IS_41) {                                  // nibbles stay 0..15: the minimum comes in through m_w * s_x
-                    lo = u32x4{q0.x & 0x0f0f0f0fu, q0.y & 0x0f0f0f0fu, q0.z & 0x0f0f0f0fu, q0.w & 0x0f0f0f0fu};
-                    hi = u32x4{(q0.x >> 4) & 0x0f0f0f0fu, (q0.y >> 4) & 0x0f0f0f0fu, (q0.z >> 4) & 0x0f0f0f0fu, (q0.w >> 4) & 0x0f0f0f0fu};
-                } else {
-                    lo = u32x4{nib_minus8(q0.x & 0x0f0f0f0fu), nib_minus8(q0.y & 0x0f0f0f0fu), nib_minus8(q0.z & 0x0f0f0f0fu), nib_minus8(q0.w & 0x0f0f0f0fu)};
-                    hi = u32x4{nib_minus8((q0.x >> 4) & 0x0f0f0f0fu), nib_minus8((q0.y >> 4) & 0x0f0f0f0fu), nib_minus8((q0.z >> 4) & 0x0f0f0f0fu), nib_minus8((q0.w >> 4) & 0x0f0f0f0fu)};
-                }
+                else if (IS_41) { lo = nib_lo(q0); hi = nib_hi(q0); }      // nibbles stay 0..15: the minimum comes in through m_w * s_x
+                else { lo = nib_minus8(nib_lo(q0)); hi = nib_minus8(nib_hi(q0)); }
                 *(u32x4 *)(Wt + row * MMQ_LD + sb * 32)      = lo;
                 *(u32x4 *)(Wt + row * MMQ_LD + sb * 32 + 16) = hi;
                 *(float *)(Ws + (sb * MMQ_BN + row) * 4) = rwd[IS_K ? 0 : t];       // dw[8][n]
@@ -308,54 +278,38 @@ __global__ void __launch_bounds__(mmq_traits<TYPE>::NW * 64, mmq_traits<TYPE>::N
             }
         }
     }
-    // ---- epilogue: dst[m][n] ----
-    if (a.epi == 1) {                      // the lane pair (2u, 2u + 1) holds gate_u and up_u of the same tokens: the even lane takes its neighbour's value and stores
-        const int64_t nv = (a.N / 2) & ~(int64_t) 7;               // ggml_vec_silu_f32: polynomial body below nv, libm tail (rows of a.N / 2 features)
+    // ---- epilogue: dst[m][n].  The form is picked once, outside the loops (as one generic lambda over the store object the two loop nests cost 4 SGPRs) ----
+    if (a.epi == 1) {
+        const mm_tile_store<MM_STORE_SILU_UP> st(a, lane);
 #pragma unroll
         for (int i = 0; i < MMQ_MI; i++)
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const int64_t n = n0 + wn + j * 16 + l15, u = n >> 1;
+                const int64_t n = n0 + wn + j * 16 + l15;
 #pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t m = m0 + wm + i * 16 + l4 * 4 + r;
-                    const float up = dpp_f<DPP_QUAD_XOR1>(acc_f[i][j][r]);
-                    if (!(lane & 1) && n + 1 < a.N && m < a.M) a.dst[m * a.ldd + u] = silu_any(acc_f[i][j][r], u < nv) * up;
-                }
+                for (int r = 0; r < 4; r++) st(m0 + wm + i * 16 + l4 * 4 + r, n, acc_f[i][j][r]);
             }
         return;
     }
+    const mm_tile_store<MM_STORE_RESID> st(a, lane);
 #pragma unroll
     for (int i = 0; i < MMQ_MI; i++)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int64_t n = n0 + wn + j * 16 + l15;
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int64_t m = m0 + wm + i * 16 + l4 * 4 + r;
-                if (n < a.N && m < a.M) a.dst[m * a.ldd + n] = a.resid ? acc_f[i][j][r] + a.resid[m * a.ldr + n] : acc_f[i][j][r];
-            }
+            for (int r = 0; r < 4; r++) st(m0 + wm + i * 16 + l4 * 4 + r, n, acc_f[i][j][r]);
         }
 }
 
 int launch_mmq(hipStream_t st, int wtype, const tview & w, const void * act, size_t act_stride, const tview & x, const tview & d, const float * resid, int64_t ldr, int epi) {
     if (opt_is_set(OPT_CLLM_NO_MMQ)) return CLLM_E_UNSUPPORTED;
-    if (d.nb[1] % 4) FAIL(CLLM_E_INVALID, "mmq: dst stride");
-    mmq_args a;
-    a.W = w.data; a.nb01 = w.nb[1]; a.N = w.ne[1]; a.K = w.ne[0];
-    a.act = (const char *) act; a.act_stride = act_stride; a.M = x.ne[1];
-    a.dst = (float *) d.data; a.ldd = d.nb[1] / 4; a.resid = resid; a.ldr = ldr; a.epi = epi;
-    if (epi && (epi != 1 || resid || a.N % 2)) FAIL(CLLM_E_INVALID, "mmq: epilogue %d", epi);
-
+    mm_tile_args a;
+    const int rc = mm_tile_args_of(a, "mmq", w, act, act_stride, x.ne[1], d, resid, ldr, epi);
+    if (rc) return rc;
     return with_tuned_type(wtype, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
-        static uint64_t attr = 0;
         constexpr int BM = (mmq_traits<T>::NW / 2) * 16 * mmq_traits<T>::MI, LDS = lds_total(BM, T == CLLM_TYPE_Q4_1);
-        if (((a.M + BM - 1) / BM) * ((a.N + MMQ_BN - 1) / MMQ_BN) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "mmq: too many tiles");
-        const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + MMQ_BN - 1) / MMQ_BN)));
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmq<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
-        hipLaunchKernelGGL(k_mmq<T>, grid, dim3(mmq_traits<T>::NW * 64), LDS, st, a);
-        LAUNCH_CHECK();
-        return CLLM_OK;
+        return mm_tile_launch<k_mmq<T>>((a.M + BM - 1) / BM, (a.N + MMQ_BN - 1) / MMQ_BN, mmq_traits<T>::NW * 64, LDS, st, a, "mmq");
     });
 }

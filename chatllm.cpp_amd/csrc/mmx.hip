@@ -19,39 +19,16 @@
 // global -> registers one step ahead, registers -> LDS (unpack to fp16) between the two barriers of a step.
 //   A operand = activations (rows = tokens), B operand = weights (cols = weight rows); D[v]: AVX lane 4 t + (v >> 2), token 4 (lane >> 4) + (v & 3), row lane & 15
 //   (layouts checked on the device by tools/micro/mfma_probe.hip)
-#include "common.h"
+#include "mm_tile.h"
 #include <stdio.h>
 #include <stdlib.h>
 
 typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-struct mmx_args {
-    const char * W; int64_t nb01; int64_t N; int64_t K;
-    const char * act; size_t act_stride; int64_t M;
-    float * dst; int64_t ldd;              // dst[m * ldd + n]
-    const float * resid; int64_t ldr;      // optional: dst = acc + resid[m * ldr + n] (the MUL_MAT -> ADD pair; resid may be dst itself)
-    int epi;                               // 1: weight rows alternate gate_u, up_u; dst[m * ldd + u] = silu(acc[2u]) * acc[2u + 1]
-};
 
 template <int TYPE> struct mmx_traits { static constexpr int MI = 2, NJ = 2, WN = 2, WM = 2; };
 template <> struct mmx_traits<CLLM_TYPE_Q4_K> { static constexpr int MI = 2, NJ = 1, WN = 4, WM = 1; };
 
-// four bytes (unsigned, one per byte of u) -> fp16 pairs 1024 + byte: (elements 0, 1), (elements 2, 3).  0x64uu is the fp16 1024 + uu (ulp 1 in [1024, 2048))
-__device__ __forceinline__ void bytes_to_h1024(uint32_t u, uint32_t & lo, uint32_t & hi) {
-    lo = __builtin_amdgcn_perm(0x64646464u, u, 0x04010400u);
-    hi = __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u);
-}
-__device__ __forceinline__ uint32_t h2_sub(uint32_t x, uint32_t c) {          // per fp16 half: x - c (exact here)
-    const h2v r = __builtin_bit_cast(h2v, x) - __builtin_bit_cast(h2v, c);
-    return __builtin_bit_cast(uint32_t, r);
-}
-__device__ __forceinline__ uint32_t h2_fma(uint32_t x, uint32_t a, uint32_t c) {   // per fp16 half: x * a + c, one rounding (exact here)
-    const h2v r = __builtin_elementwise_fma(__builtin_bit_cast(h2v, x), __builtin_bit_cast(h2v, a), __builtin_bit_cast(h2v, c));
-    return __builtin_bit_cast(uint32_t, r);
-}
 // four int8 -> four fp16 of the same integers (two dwords)
 __device__ __forceinline__ u32x2 i8x4_to_h(uint32_t x) {
     uint32_t lo, hi;
@@ -71,19 +48,15 @@ template <int OFF> __device__ __forceinline__ u32x2 nib4_to_h(uint32_t nb) {
     return u32x2{h2_sub(lo, C), h2_sub(hi, C)};
 }
 // 16 nibble bytes -> 16 fp16
-template <int OFF> __device__ __forceinline__ void nib16_to_h(uint32_t n0, uint32_t n1, uint32_t n2, uint32_t n3, u32x4 & o0, u32x4 & o1) {
-    const u32x2 a = nib4_to_h<OFF>(n0), b = nib4_to_h<OFF>(n1), c = nib4_to_h<OFF>(n2), d = nib4_to_h<OFF>(n3);
+template <int OFF> __device__ __forceinline__ void nib16_to_h(const u32x4 n, u32x4 & o0, u32x4 & o1) {
+    const u32x2 a = nib4_to_h<OFF>(n.x), b = nib4_to_h<OFF>(n.y), c = nib4_to_h<OFF>(n.z), d = nib4_to_h<OFF>(n.w);
     o0 = u32x4{a.x, a.y, b.x, b.y}; o1 = u32x4{c.x, c.y, d.x, d.y};
 }
-__device__ __forceinline__ uint32_t h2_splat(float v) { const _Float16 h = (_Float16) v; uint16_t b; __builtin_memcpy(&b, &h, 2); return (uint32_t) b * 0x00010001u; }
-#ifdef MMX_SCALAR_FMA        // (A/B: two v_fma_f32 instead of one v_pk_fma_f32; build the file with -fno-slp-vectorize)
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return f32x2{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
-#else
+// two serial fp32 chains per instruction (v_pk_fma_f32); two v_fma_f32 instead measured equal (5279 against 5207 us on the gate/up GEMM: DESIGN.md section 8)
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-#endif
 
 template <int TYPE>
-__global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
+__global__ void __launch_bounds__(256, 2) k_mmx(const mm_tile_args a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using T = mmx_traits<TYPE>;
     constexpr bool IS_K = TYPE == CLLM_TYPE_Q4_K, IS_41 = TYPE == CLLM_TYPE_Q4_1, IS_Q8 = TYPE == CLLM_TYPE_Q8_0;
@@ -122,8 +95,7 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
         }
 
     // ---- staging: global -> registers (one K step ahead), registers -> LDS (unpack to fp16) ----
-    constexpr int BS = (int) wtype_size(TYPE), QOFF = IS_41 ? 4 : 2;
-    struct __attribute__((packed, aligned(2))) q16 { uint32_t x, y, z, w; };
+    constexpr int BS = (int) wtype_size(TYPE);
     constexpr int CPR = KS / 16;                                    // 16-byte chunks of int8 per token and stage
     constexpr int NXA = BM * CPR / NT;                              // activation tasks per thread: (token, 16 int8)
     constexpr int NXS = IS_K ? 1 : (BM * XPL + NT - 1) / NT;        // activation scale tasks (Q4_K: dx and the eight sub-block sums of token tid % BM ... see below)
@@ -133,12 +105,7 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
     // a conversion here would make the prefetch wait for its own loads (s_waitcnt right behind them) and the global latency would sit in front of every K step
     auto prefetch = [&](int64_t k0) {
 #pragma unroll
-        for (int t = 0; t < NXA; t++) {
-            const int c = tid + NT * t, row = c / CPR, ch = c % CPR;
-            const int64_t m = m0 + row;
-            rx[t] = u32x4{0, 0, 0, 0};
-            if (m < a.M && k0 + ch * 16 < K) rx[t] = *(const u32x4 *)(a.act + m * a.act_stride + k0 + ch * 16);
-        }
+        for (int t = 0; t < NXA; t++) rx[t] = act_chunk_load<CPR>(a, m0, k0, tid + NT * t);
         if constexpr (IS_K) {          // thread (token = tid % BM, k = tid / BM) for tid < 4 BM: S[2k], S[2k+1]; k == 0 also dx
             rxs[0] = rxs[1] = rxs[2] = 0;
             if (tid < 4 * BM) {
@@ -156,11 +123,7 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
             for (int t = 0; t < NXS; t++) {                         // dx[8][m] (Q4_1: then sx[8][m], the f32 s plane)
                 const int c = tid + NT * t;
                 rxs[t] = 0;
-                if (c < BM * XPL) {
-                    const int row = c % BM, pl = c / BM, sb = pl % NBK;
-                    const int64_t m = m0 + row;
-                    if (m < a.M && k0 + sb * 32 < K) rxs[t] = *(const uint32_t *)(a.act + m * a.act_stride + (pl < NBK ? act_d : act_s) + ((k0 / 32) + sb) * 4);
-                }
+                if (c < BM * XPL) rxs[t] = act_scale_load<BM, NBK>(a, m0, k0, act_d, act_s, c);
             }
         }
 #pragma unroll
@@ -171,22 +134,14 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
                 const int row = c >> 2, c4 = c & 3;
                 const int64_t n = n0 + row;
                 rw2[t] = u32x4{0, 0, 0, 0}; rwh[t] = u32x4{0, 0, 0, 0};
-                if (n < a.N) {
-                    const char * bp = a.W + n * a.nb01 + (k0 / 256) * 144;
-                    rwh[t] = *(const u32x4 *) bp;
-                    rw[t]  = *(const u32x4 *)(bp + 16 + 32 * c4);
-                    rw2[t] = *(const u32x4 *)(bp + 32 + 32 * c4);
-                }
+                if (n < a.N) { const wchunk_q4k r = wchunk_q4k_load(a.W + n * a.nb01 + (k0 / 256) * 144, c4); rwh[t] = r.h; rw[t] = r.q; rw2[t] = r.q2; }
             } else {                                                // (row, 32-block sb)
                 const int row = c / NBK, sb = c % NBK;
                 const int64_t n = n0 + row, b = k0 / 32 + sb;
                 rwd[IS_K ? 0 : t] = 0; if (IS_Q8) rw2[IS_Q8 ? t : 0] = u32x4{0, 0, 0, 0};
                 if (n < a.N && b * 32 < K) {
-                    const char * bp = a.W + n * a.nb01 + b * BS;
-                    if (IS_41) rwd[IS_K ? 0 : t] = *(const uint32_t *) bp; else rwd[IS_K ? 0 : t] = *(const uint16_t *) bp;
-                    const q16 q0 = *(const q16 *)(bp + QOFF);
-                    rw[t] = u32x4{q0.x, q0.y, q0.z, q0.w};
-                    if (IS_Q8) { const q16 q1 = *(const q16 *)(bp + 18); rw2[IS_Q8 ? t : 0] = u32x4{q1.x, q1.y, q1.z, q1.w}; }
+                    const wblock32_raw r = wblock32_load<TYPE>(a.W + n * a.nb01 + b * BS);
+                    rwd[IS_K ? 0 : t] = r.d; rw[t] = r.q; if (IS_Q8) rw2[IS_Q8 ? t : 0] = r.q2;
                 }
             }
         }
@@ -222,23 +177,20 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
             if constexpr (IS_K) {
                 const int row = c >> 2, c4 = c & 3;
                 const u32x4 h = rwh[t];
-                const uint32_t u0 = h.y & 0x3f3f3f3fu, u2 = h.z & 0x3f3f3f3fu;
-                const uint32_t u1 = (h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4);
-                const uint32_t u3 = ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4);
-                const uint32_t scp = ((c4 & 2) ? u1 : u0) >> ((c4 & 1) * 16), mnp = ((c4 & 2) ? u3 : u2) >> ((c4 & 1) * 16);
+                const q4k_scales_t u = q4k_scales(h.y, h.z, h.w);
+                const uint32_t scp = ((c4 & 2) ? u.u1 : u.u0) >> ((c4 & 1) * 16), mnp = ((c4 & 2) ? u.u3 : u.u2) >> ((c4 & 1) * 16);
                 const float sc_lo = (float)(scp & 0xff), sc_hi = (float)((scp >> 8) & 0xff), m_lo = (float)(mnp & 0xff), m_hi = (float)((mnp >> 8) & 0xff);
                 const uint32_t slo = h2_splat(sc_lo), shi = h2_splat(sc_hi);
                 const uint32_t clo = h2_splat(-1024.0f * sc_lo), chi = h2_splat(-1024.0f * sc_hi);      // (1024 + nib) * sc - 1024 sc = nib * sc, one rounding, exact
-                const uint32_t q[8] = { rw[t].x, rw[t].y, rw[t].z, rw[t].w, rw2[t].x, rw2[t].y, rw2[t].z, rw2[t].w };
+                const u32x4 ql[2] = { nib_lo(rw[t]), nib_lo(rw2[t]) }, qh[2] = { nib_hi(rw[t]), nib_hi(rw2[t]) };
                 char * wr = Wt + row * LD + c4 * 128;               // elements 64 c4 .. : 32 low-nibble weights (sub-block 2 c4), then 32 high-nibble weights (2 c4 + 1)
 #pragma unroll
                 for (int p = 0; p < 2; p++) {
                     uint32_t lo[8], hi[8];
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        const uint32_t x = q[4 * p + e];
                         uint32_t a0, a1, b0, b1;
-                        bytes_to_h1024(x & 0x0f0f0f0fu, a0, a1); bytes_to_h1024((x >> 4) & 0x0f0f0f0fu, b0, b1);
+                        bytes_to_h1024(ql[p][e], a0, a1); bytes_to_h1024(qh[p][e], b0, b1);
                         lo[2 * e] = h2_fma(a0, slo, clo); lo[2 * e + 1] = h2_fma(a1, slo, clo); hi[2 * e] = h2_fma(b0, shi, chi); hi[2 * e + 1] = h2_fma(b1, shi, chi);
                     }
                     *(u32x4 *)(wr + p * 32)      = u32x4{lo[0], lo[1], lo[2], lo[3]}; *(u32x4 *)(wr + p * 32 + 16)      = u32x4{lo[4], lo[5], lo[6], lo[7]};
@@ -256,8 +208,8 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
                     i8x16_to_h(q0, o[0], o[1]); i8x16_to_h(rw2[IS_Q8 ? t : 0], o[2], o[3]);
                 } else {
                     constexpr int OFF = IS_41 ? 0 : 8;              // elements 0..15 = low nibbles, 16..31 = high nibbles
-                    nib16_to_h<OFF>(q0.x & 0x0f0f0f0fu, q0.y & 0x0f0f0f0fu, q0.z & 0x0f0f0f0fu, q0.w & 0x0f0f0f0fu, o[0], o[1]);
-                    nib16_to_h<OFF>((q0.x >> 4) & 0x0f0f0f0fu, (q0.y >> 4) & 0x0f0f0f0fu, (q0.z >> 4) & 0x0f0f0f0fu, (q0.w >> 4) & 0x0f0f0f0fu, o[2], o[3]);
+                    nib16_to_h<OFF>(nib_lo(q0), o[0], o[1]);
+                    nib16_to_h<OFF>(nib_hi(q0), o[2], o[3]);
                 }
                 char * wr = Wt + row * LD + sb * 64;
                 *(u32x4 *)(wr) = o[0]; *(u32x4 *)(wr + 16) = o[1]; *(u32x4 *)(wr + 32) = o[2]; *(u32x4 *)(wr + 48) = o[3];
@@ -270,18 +222,12 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int frag_off = l15 * LD + l4 * 8;                         // row l15 of a patch, AVX lane l4 of the instruction's four
     prefetch(0);
+    // (the loop taken apart on the gate/up GEMM, Q4_0: compute on one staged step 4.08 ms, staging without compute 1.57 ms, both 5.2 ms -- DESIGN.md section 8)
     for (int64_t k0 = 0; k0 < K; k0 += KS) {
-#ifdef MMX_NOSTAGE           // (timing experiments only: stage the first step, compute on it for every step)
-        if (k0 == 0) { __syncthreads(); commit(); __syncthreads(); }
-#else
         __syncthreads();                                            // the previous step's fragments are consumed
         commit();
         __syncthreads();
         if (k0 + KS < K) prefetch(k0 + KS);
-#endif
-#ifdef MMX_NOCOMPUTE
-        continue;
-#endif
 
         if constexpr (IS_K) {
 #pragma unroll
@@ -375,7 +321,7 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
     }
 
     // ---- epilogue: hsum_float_8 (arch/x86/quants.c:43-49) (+ mins / summs), dst[m][n] ----
-    const int64_t nv = (a.N / 2) & ~(int64_t) 7;
+    const mm_tile_store<MM_STORE_SILU_UP> st_silu(a, lane); const mm_tile_store<MM_STORE_RESID> st_resid(a, lane);
 #pragma unroll
     for (int i = 0; i < MI; i++)
 #pragma unroll
@@ -396,11 +342,7 @@ __global__ void __launch_bounds__(256, 2) k_mmx(const mmx_args a) {
                 }
                 if (IS_41) v = v + summs[IS_41 ? i : 0][IS_41 ? j : 0][r >> 1][r & 1];
                 const int64_t m = m0 + wm + i * 16 + l4 * 4 + r;
-                if (a.epi == 1) {           // the lane pair (2u, 2u + 1) holds gate_u and up_u of the same token: the even lane takes its neighbour's value and stores
-                    const float up = dpp_f<DPP_QUAD_XOR1>(v);
-                    const int64_t u = n >> 1;
-                    if (!(lane & 1) && n + 1 < a.N && m < a.M) a.dst[m * a.ldd + u] = silu_any(v, u < nv) * up;
-                } else if (n < a.N && m < a.M) a.dst[m * a.ldd + n] = a.resid ? v + a.resid[m * a.ldr + n] : v;
+                if (a.epi == 1) st_silu(m, n, v); else st_resid(m, n, v);
             }
         }
 }
@@ -415,12 +357,9 @@ template <int TYPE> static constexpr int mmx_lds() {
 
 // the exact-order mat-mul: any M >= 1; K % 32 == 0 (Q4_K: % 256); CLLM_E_UNSUPPORTED: not this kernel's type
 int launch_mmx(hipStream_t st, int wtype, const tview & w, const void * act, size_t act_stride, const tview & x, const tview & d, const float * resid, int64_t ldr, int epi) {
-    if (d.nb[1] % 4) FAIL(CLLM_E_INVALID, "mmx: dst stride");
-    mmx_args a;
-    a.W = w.data; a.nb01 = w.nb[1]; a.N = w.ne[1]; a.K = w.ne[0];
-    a.act = (const char *) act; a.act_stride = act_stride; a.M = x.ne[1];
-    a.dst = (float *) d.data; a.ldd = d.nb[1] / 4; a.resid = resid; a.ldr = ldr; a.epi = epi;
-    if (epi && (epi != 1 || resid || a.N % 2)) FAIL(CLLM_E_INVALID, "mmx: epilogue %d", epi);
+    mm_tile_args a;
+    const int rc = mm_tile_args_of(a, "mmx", w, act, act_stride, x.ne[1], d, resid, ldr, epi);
+    if (rc) return rc;
     static const bool dbg = opt_is_set(OPT_CLLM_DEBUG);
     if (dbg) {
         int nb = 0;
@@ -429,13 +368,7 @@ int launch_mmx(hipStream_t st, int wtype, const tview & w, const void * act, siz
     }
     return with_tuned_type(wtype, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
-        static uint64_t attr = 0;
-        using TR = mmx_traits<T>; constexpr int BN = TR::WN * TR::NJ * 16, BM = TR::WM * TR::MI * 16, LDS = mmx_lds<T>();
-        if (((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "mmx: too many tiles");
-        const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)));
-        if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_mmx<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); dev_flag_set(attr); }
-        hipLaunchKernelGGL(k_mmx<T>, grid, dim3(256), LDS, st, a);
-        LAUNCH_CHECK();
-        return CLLM_OK;
+        using TR = mmx_traits<T>; constexpr int BN = TR::WN * TR::NJ * 16, BM = TR::WM * TR::MI * 16;
+        return mm_tile_launch<k_mmx<T>>((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, 256, mmx_lds<T>(), st, a, "mmx");
     });
 }

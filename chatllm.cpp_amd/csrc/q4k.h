@@ -15,6 +15,7 @@
 // every two steps (16 super-blocks), lanes 0..11 walk the records in block order -- lanes 0..7 carry acc[], lanes 8..11 acc_m[].
 #pragma once
 #include "common.h"
+#include "q4k_scales.h"
 
 #define DPP_ROW_SHL4 0x104
 #define DPP_ROW_SHR4 0x114
@@ -37,7 +38,7 @@ struct q4k_sel {
     bool hi, mhi, b2, b4, wm;
 };
 
-// lane-constant selectors (get_scale_min_k4, ggml-quants.c:703-711, after the utmp shuffle of arch/x86/quants.c:1773-1778)
+// lane-constant selectors (over q4k_scales' words, after the utmp shuffle of arch/x86/quants.c:1773-1778)
 __device__ __forceinline__ q4k_sel q4k_lane_sel(int lane) {
     q4k_sel L;
     const int j = lane & 7, g = lane >> 3, p = j >> 1;
@@ -59,14 +60,10 @@ __device__ __forceinline__ q4k_sel q4k_lane_sel(int lane) {
 __device__ __forceinline__ void q4k_emit(const u32x4 h, const u32x4 q, const char * ar, int off_d, int off_s, int bb, bool ok, const q4k_sel & L, char * rec) {
     const float d    = h2f((uint16_t)(h.x & 0xffff));
     const float dmin = h2f((uint16_t)(h.x >> 16));
-    // 6-bit unpack: u0 = sc[0..3], u1 = sc[4..7], u2 = m[0..3], u3 = m[4..7]
-    const uint32_t u0 = h.y & 0x3f3f3f3fu;
-    const uint32_t u2 = h.z & 0x3f3f3f3fu;
-    const uint32_t u1 = (h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4);
-    const uint32_t u3 = ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4);
-    const uint32_t scp = (L.hi ? u1 : u0) >> L.sh16;
+    const q4k_scales_t u = q4k_scales(h.y, h.z, h.w);
+    const uint32_t scp = (L.hi ? u.u1 : u.u0) >> L.sh16;
     const int sc_lo = (int)(scp & 0xff), sc_hi = (int)((scp >> 8) & 0xff);
-    const int mj    = (int)(((L.mhi ? u3 : u2) >> L.sh8) & 0xff);
+    const int mj    = (int)(((L.mhi ? u.u3 : u.u2) >> L.sh8) & 0xff);
     const u32x4 al = *(const u32x4 *)(ar + bb * 256 + L.a_off);
     const u32x4 ah = *(const u32x4 *)(ar + bb * 256 + L.a_off + 32);
     const float yd = ((const float *)(ar + off_d))[bb];
@@ -87,22 +84,14 @@ __device__ __forceinline__ void q4k_emit(const u32x4 h, const u32x4 q, const cha
     const int s0 = L.b2 ? t0 : t2, s1 = L.b2 ? t1 : t3;
     k0 += dpp_i<DPP_QUAD_XOR2>(s0); k1 += dpp_i<DPP_QUAD_XOR2>(s1);
     const int keep = L.b4 ? k1 : k0, send = L.b4 ? k0 : k1;
-#ifdef Q4K_NOSCATTER     // (timing experiments only)
-    const int sumi = (t0 + t1) + (t2 + t3) + (keep & 0) + (send & 0);
-#else
     const int sumi = keep + lane_xor4_i(send);
-#endif
     // mins: prod[k] = m[2k] S[2k] + m[2k+1] S[2k+1] on the lane pair
     int pm = __mul24(mj, ys);                   // |ys| <= 32 * 127
     pm += dpp_i<DPP_QUAD_XOR1>(pm);
     float x = (float) sumi, dd = yd * d, xm = (float) pm, dm = (-yd) * dmin;
     if (!ok) { dd = 0.0f; dm = 0.0f; }           // a masked block: fma(0, x, acc) == acc for the finite x it carries (two selects instead of four)
-#ifdef Q4K_NOWRITE       // (timing experiments only)
-    asm volatile("" :: "v"(x), "v"(dd), "v"(xm), "v"(dm), "v"(rec));
-#else
     *(float2 *)(rec + L.w_off) = float2{x, dd};
-    *(float2 *)(rec + L.wm_off) = float2{xm, dm};
-#endif       // (both lanes of the pair hold the same record: no branch)
+    *(float2 *)(rec + L.wm_off) = float2{xm, dm};       // (both lanes of the pair hold the same record: no branch)
 }
 
 // ---- the same records from FOUR lanes per super-block (the decode mat-vec, gemv_decode.hip): lane j owns the whole 64-weight chunk j (32 quant
@@ -125,11 +114,8 @@ __device__ __forceinline__ q4k_sel4 q4k_lane_sel4(int lane) {
 __device__ __forceinline__ void q4k_emit4(const u32x4 h, const u32x4 qa, const u32x4 qb, const char * ar, int off_d, int off_s, int bb, bool ok, const q4k_sel4 & L, char * rec) {
     const float d    = h2f((uint16_t)(h.x & 0xffff));
     const float dmin = h2f((uint16_t)(h.x >> 16));
-    const uint32_t u0 = h.y & 0x3f3f3f3fu;
-    const uint32_t u2 = h.z & 0x3f3f3f3fu;
-    const uint32_t u1 = (h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4);
-    const uint32_t u3 = ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4);
-    const uint32_t scp = (L.hi ? u1 : u0) >> L.sh16, mnp = (L.hi ? u3 : u2) >> L.sh16;
+    const q4k_scales_t u = q4k_scales(h.y, h.z, h.w);
+    const uint32_t scp = (L.hi ? u.u1 : u.u0) >> L.sh16, mnp = (L.hi ? u.u3 : u.u2) >> L.sh16;
     const int sc_lo = (int)(scp & 0xff), sc_hi = (int)((scp >> 8) & 0xff), m_lo = (int)(mnp & 0xff), m_hi = (int)((mnp >> 8) & 0xff);
     const char * ab = ar + bb * 256 + L.a_off;
     const u32x4 al0 = *(const u32x4 *) ab, al1 = *(const u32x4 *)(ab + 16), ah0 = *(const u32x4 *)(ab + 32), ah1 = *(const u32x4 *)(ab + 48);

@@ -688,6 +688,43 @@ def test_mul_mat_ex_equals_the_node_sequences(gpu, t, K, N, M):
         assert np.array_equal(bits(ops.mul_mat_ex(w, x2, pro=3)), bits(want_p))
 
 
+@pytest.mark.parametrize("mode", [1, 0], ids=["exact", "fast"])
+@pytest.mark.parametrize("t,K,N,M", [(O.Q4_0, 288, 130, 65), (O.Q4_1, 288, 130, 65), (O.Q8_0, 288, 130, 65), (O.Q4_K, 512, 130, 65)])
+def test_mul_mat_ex_epilogues_into_strided_rows(gpu, mode, t, K, N, M):
+    """the tile GEMMs' shared store (mm_tile.h) with ldd != ldr != N, in k_mmx (exact) and k_mmq (fast): dst rows N + 7 floats wide, residual rows N + 5 wide, the
+    SiLU * up form into rows N / 2 + 3 wide -- bit for bit the same mode's node sequences, every padding word and the whole residual buffer untouched.  K = 288 is no
+    multiple of either K stage, N = 130 is ragged in both row tiles, M = 65 is one token past a 64-token tile; N / 2 = 65: feature 64 takes SiLU's libm tail"""
+    ops, T = gpu.ops, gpu.Tensor
+    r_ = np.random.default_rng([23, t, K, N, M])
+    w = T.from_numpy(rand_blocks(t, N, K, r_), t, [K, N])
+    x = T.from_numpy(r_.standard_normal((M, K)).astype(np.float32))
+    nan_fill = lambda rows, cols: (np.arange(rows * cols, dtype=np.uint32) | 0x7fc00000).view(np.float32).reshape(rows, cols)      # NaNs with the index as payload
+    u32 = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    with prefill_mode(gpu, mode):
+        y = ops.mul_mat(w, x)                                                      # [N, M]
+        # the residual form
+        fill_d, rh = nan_fill(M, N + 7), nan_fill(M, N + 5)
+        rh[:, :N] = r_.standard_normal((M, N)).astype(np.float32)
+        dbuf, rbuf = T.from_numpy(fill_d), T.from_numpy(rh)
+        r_view = rbuf.view([N, M], [4, (N + 5) * 4])
+        ops.mul_mat_ex(w, x, resid=r_view, dst=dbuf.view([N, M], [4, (N + 7) * 4]))
+        want = ops.add(y, ops.cont(r_view)).numpy()
+        out = dbuf.numpy()
+        assert np.array_equal(u32(out[:, :N]), u32(want))
+        assert np.array_equal(u32(out[:, N:]), u32(fill_d[:, N:]))
+        assert np.array_equal(u32(rbuf.numpy()), u32(rh))
+        # the SiLU * up form: weight rows alternate gate_u, up_u
+        H = N // 2
+        fill_s = nan_fill(M, H + 3)
+        sbuf = T.from_numpy(fill_s)
+        ops.mul_mat_ex(w, x, epi=1, dst=sbuf.view([H, M], [4, (H + 3) * 4]))
+        gate = y.view([H, M], [8, y.nb[1]], offset=0); up = y.view([H, M], [8, y.nb[1]], offset=4)
+        want_s = ops.mul(ops.silu(ops.cont(gate)), ops.cont(up)).numpy()
+        out_s = sbuf.numpy()
+        assert np.array_equal(u32(out_s[:, :H]), u32(want_s))
+        assert np.array_equal(u32(out_s[:, H:]), u32(fill_s[:, H:]))
+
+
 @pytest.mark.parametrize("t,K,ne,k", [(O.Q4_K, 4096, 8, 2), (O.Q4_K, 256, 8, 2), (O.Q8_0, 512, 4, 2), (O.Q4_0, 1024, 16, 3), (O.Q4_1, 256, 60, 6),
                                       (O.Q4_K, 14336, 64, 8), (O.Q4_0, 4096, 7, 1), (O.Q8_0, 8192, 33, 4)])
 def test_moe_router_equals_the_node_sequence(gpu, t, K, ne, k):
