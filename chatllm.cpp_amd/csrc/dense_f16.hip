@@ -10,6 +10,11 @@
 // error, an fp16 rounding of the weights instead.  Off by default (the default prefill is the exact-order path, mmx.hip); tests/test_gpu_ops.py checks it
 // against the oracle's dequantize + float64 GEMM with a stated tolerance.
 //
+// Range: a weight is FORMED in fp16, so a block whose dequantized magnitude passes 65504 (a scale field near the top of fp16 times a quant above 1) overflows to
+// +-inf here by construction where the exact and fast paths, which keep the scale in fp32, stay finite.  Model files hold no such scales; the weight-edge tests
+// (tests/test_gpu_weight_edges.py) therefore run their `large` profile on the exact and fast paths only.  At the other end the staging's packed-half arithmetic and the matrix cores' inputs KEEP fp16
+// subnormals (measured by those tests: scale fields 0x0001..0x03ff land inside the mirror's bound, which a flush of those weights to zero would miss).
+//
 // Tiling: 128 x 128 or 256 x 256 (weight rows n x tokens m: the launcher's pick, below) per 256-thread workgroup, K walked 64 elements per stage, two LDS stages (one barrier per stage: the next
 // stage is written while the current one feeds the matrix cores), global -> registers one stage ahead (raw bytes: nothing converted before the data is
 // needed), 144-byte tile rows (conflict-free ds_read_b128 fragments).  A wave owns 2 x 2 or 4 x 4 MFMA tiles (accumulators in AGPRs).  A operand = tokens, B operand = weight rows:
