@@ -13,30 +13,10 @@
 // k_soft_max's.  Only WHICH workgroup computes an element differs from k_attn_dec / the unfused MUL_MAT + SOFT_MAX nodes, so the
 // results are bit-identical to theirs -- and to libggml-cpu.so -- at every context length.  Used by the runner above CLLM_ATTN_LONG
 // cached positions (default and minimum 512).
-#include "common.h"
-
-#include "q4k.h"
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-
-// GGML_F32x8_REDUCE over the 32 accumulators held two per lane by 16 lanes (decode_fused.hip's vd32_reduce: the same definition)
-__device__ __forceinline__ float al_xor4(float v) { return __int_as_float(lane_xor4_i(__float_as_int(v))); }
-__device__ __forceinline__ float al_vd32_reduce(float a0, float a1) {
-    a0 = a0 + dpp_f<DPP_ROW_ROR8>(a0); a1 = a1 + dpp_f<DPP_ROW_ROR8>(a1);
-    a0 = a0 + al_xor4(a0);             a1 = a1 + al_xor4(a1);
-    a0 = a0 + dpp_f<DPP_QUAD_XOR2>(a0); a1 = a1 + dpp_f<DPP_QUAD_XOR2>(a1);
-    const float u = a0 + a1;
-    return u + dpp_f<DPP_QUAD_XOR1>(u);
-}
+#include "attn_token.h"
 
 static unsigned long long * g_long_ts = nullptr;
 extern "C" __attribute__((visibility("default"))) void cllm_debug_set_attn_long_ts(unsigned long long * dev_buf) { g_long_ts = dev_buf; }   // tools only
-#define TS(k) do { if (ts && threadIdx.x == 0) ts[(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = wall_clock64(); } while (0)
-
-__device__ __forceinline__ int uniform_load_i32_(const int32_t * p) {
-    int v;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
 
 // ---- (1) RoPE + cache write + scores -------------------------------------------------------------------------------------------
 template <int HD, int MODE, int R2>
@@ -49,7 +29,7 @@ __global__ void __launch_bounds__(256) k_attn_long_scores(const float * __restri
     constexpr int half = HD / 2, off = rope_pair(MODE, 0, half).off, U = 4;
     const int g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int KD = nkv * HD, QD = nh * HD;
-    const int pos = uniform_load_i32_(pos_dev), n_kv = pos + 1;
+    const int pos = uniform_load_i32(pos_dev), n_kv = pos + 1;
     // slice of positions of this workgroup: rounded up to whole passes of 4 waves x 4 rows x U
     constexpr int PASS = 4 * 4 * U;
     const int chunk = (((n_kv + (int) gridDim.x - 1) / (int) gridDim.x + PASS - 1) / PASS) * PASS;
@@ -59,12 +39,11 @@ __global__ void __launch_bounds__(256) k_attn_long_scores(const float * __restri
     // the first pass of K rows depends only on the position: requested before the RoPE work (its latency overlaps the projections' loads and the rotation)
     constexpr int NCH = HD / 32, RPI = 4 * U;
     const int c16 = lane & 15, sub = lane >> 4;
-    const uint16_t * kbase = k_cache + g * HD + 2 * c16;
     auto load_rows = [&](int ib, uint32_t (&r)[U][NCH]) {        // unconditional (clamped): exact vmcnt bookkeeping
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int i0 = ib + u * 4 + sub;
-            const uint16_t * kr = kbase + (int64_t)(i0 < pos ? i0 : 0) * KD;
+            const uint16_t * kr = k_slot(k_cache, i0 < pos ? i0 : 0, KD, g, HD, 2 * c16);
 #pragma unroll
             for (int i = 0; i < NCH; i++) r[u][i] = *(const uint32_t *)(kr + 32 * i);
         }
@@ -76,17 +55,14 @@ __global__ void __launch_bounds__(256) k_attn_long_scores(const float * __restri
     for (int t = tid; t < (R2 + 1) * half; t += 256) {          // pairs of the r2 query heads, then of k
         const int which = t / half, i = t - which * half, ic = rope_pair(MODE, i, half).ic;
         const float * x = which < R2 ? qkv + (g * R2 + which) * HD : qkv + QD + g * HD;
-        const float x0 = x[ic], x1 = x[ic + off], c = rope_cs[2 * i], s_ = rope_cs[2 * i + 1];
-        const float y0 = rope_rot_a(x0, x1, c, s_), y1 = rope_rot_b(x0, x1, c, s_);
-        float * o = which < R2 ? qs + which * HD : knew;
-        o[ic] = h2f(f2h(y0)); o[ic + off] = h2f(f2h(y1));
+        token_rope_round(x[ic], x[ic + off], ic, off, rope_cs[2 * i], rope_cs[2 * i + 1], which < R2 ? qs + which * HD : knew);
     }
     for (int d = tid; d < HD; d += 256) vnew[d] = h2f(f2h(qkv[QD + KD + g * HD + d]));
     __syncthreads();
     if (blockIdx.x == 0) {
         for (int d = tid; d < HD; d += 256) {
-            k_cache[(int64_t) pos * KD + g * HD + d] = f2h(knew[d]);
-            v_cache[((int64_t) g * HD + d) * ML + pos] = f2h(vnew[d]);
+            *k_slot(k_cache, pos, KD, g, HD, d) = f2h(knew[d]);
+            *v_slot(v_cache, g, HD, d, ML, pos) = f2h(vnew[d]);
         }
     }
 
@@ -117,7 +93,7 @@ __global__ void __launch_bounds__(256) k_attn_long_scores(const float * __restri
                 float a0 = 0.0f, a1 = 0.0f;
 #pragma unroll
                 for (int i = 0; i < NCH; i++) { a0 = __builtin_fmaf(k0[i], qa[h][i], a0); a1 = __builtin_fmaf(k1[i], qb[h][i], a1); }
-                const float v = al_vd32_reduce(a0, a1);
+                const float v = vd32_reduce(a0, a1);
                 if (c16 == 0 && i0 < i_hi) S[(int64_t)(g * R2 + h) * ML + i0] = v * scale;          // the SCALE node
             }
         }
@@ -135,33 +111,13 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax(const int32_t * __re
     __shared__ double red_d[1];
     __shared__ float  red_f[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_kv = uniform_load_i32_(pos_dev) + 1, nv = n_kv & ~7;
+    const int n_kv = uniform_load_i32(pos_dev) + 1;
     const float * row = S + (int64_t) blockIdx.x * ML;
     uint16_t * prow = P16 + (int64_t) blockIdx.x * ML;
     float * sc = sm; float * gsum = sm + ML;
     float mx = -INFINITY;
     for (int i = tid; i < n_kv; i += 1024) { const float v = row[i]; sc[i] = v; mx = fmaxf(mx, v); }
-    mx = wave_max(mx);
-    if (lane == 0) red_f[wave] = mx;
-    __syncthreads();
-    mx = red_f[0];
-#pragma unroll
-    for (int w = 1; w < 16; w++) mx = fmaxf(mx, red_f[w]);
-    // every wave exponentiates; the per-group float sums are then accumulated by ONE wave in k_soft_max's order
-    // (lane l owns groups l, l + 64, ...; double accumulation; DPP tree) -> the node kernel's bits
-    for (int gi = tid * 8; gi < nv; gi += 1024 * 8) {
-        float e[8];
-#pragma unroll
-        for (int l = 0; l < 8; l++) { e[l] = ggml_expf_poly(sc[gi + l] - mx); sc[gi + l] = e[l]; }
-        gsum[gi >> 3] = soft_group8_sum(e);
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const double rinv = soft_total_rinv_groups(gsum, nv >> 3, sc, nv, n_kv, mx, n_kv >> 3, lane);
-        if (lane == 0) red_d[0] = rinv;
-    }
-    __syncthreads();
-    const float inv = (float) red_d[0];
+    const float inv = long_soft_max(mx, sc, gsum, n_kv, red_f, red_d, tid, lane, wave);
     for (int i = tid; i < n_kv; i += 1024) prow[i] = f2h(sc[i] * inv);          // the fp16 rounding src1 of V.P gets (exact in fp32 later)
 }
 
@@ -176,10 +132,10 @@ __global__ void __launch_bounds__(256) k_attn_long_pv(const int32_t * __restrict
     extern __shared__ __attribute__((aligned(16))) uint16_t psm[]; // [n_kv rounded up to 8] fp16 probabilities of this head
     __shared__ float tail[16][32];
     const int g = blockIdx.y, r2 = gridDim.z, h = g * r2 + blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_kv = uniform_load_i32_(pos_dev) + 1, np = n_kv & ~31, nch = np >> 5, ntail = n_kv - np;
+    const int n_kv = uniform_load_i32(pos_dev) + 1, np = n_kv & ~31, nch = np >> 5, ntail = n_kv - np;
     const int c16 = lane & 15, sub = lane >> 4, rl = wave * 4 + sub, d0 = blockIdx.x * 16 + rl;
-    const uint16_t * vr = v_cache + ((int64_t) g * HD + d0) * ML + 2 * c16;
-    constexpr int UC = 16;                                        // chunks in flight per lane
+    const uint16_t * vr = v_slot(v_cache, g, HD, d0, ML, 2 * c16);
+    constexpr int UC = 16;                                       // chunks in flight per lane
     uint32_t ring[UC];
 #pragma unroll
     for (int c = 0; c < UC; c++) ring[c] = *(const uint32_t *)(vr + 32 * (c < nch ? c : 0));
@@ -188,13 +144,9 @@ __global__ void __launch_bounds__(256) k_attn_long_pv(const int32_t * __restrict
     for (int i = tid * 8; i < n_kv; i += 256 * 8) *(u32x4 *)(psm + i) = *(const u32x4 *)(prow + i);      // (ML % 8 == 0: whole 16-byte chunks are inside the row)
     __syncthreads();
     float a0 = 0.0f, a1 = 0.0f;
-    // both operands are fp16 in registers: fma((float) v, (float) p, acc) is one v_fma_mix_f32 (the conversions are exact: the cvt + fma of the other kernels bit for bit)
     const uint32_t * pp = (const uint32_t *) psm + c16;
     const uint32_t * vp = (const uint32_t *) vr;
-    auto step = [&](uint32_t vw, uint32_t pw) {
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "+v"(a0) : "v"(vw), "v"(pw));      // low halves
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(a1) : "v"(vw), "v"(pw));      // high halves
-    };
+    auto step = [&](uint32_t vw, uint32_t pw) { fma_mix_pair(a0, a1, vw, pw); };
     int i0 = 0;
     for (; i0 + 2 * UC <= nch; i0 += UC) {                        // whole groups whose refills are inside the row: no clamps, immediate offsets
 #pragma unroll
@@ -213,15 +165,7 @@ __global__ void __launch_bounds__(256) k_attn_long_pv(const int32_t * __restrict
             if (i < nch) step(cur, pp[16 * i]);
         }
     }
-    const float res = al_vd32_reduce(a0, a1);
-    if (2 * c16 < ntail)     tail[rl][2 * c16]     = h2f(t0) * h2f(psm[np + 2 * c16]);
-    if (2 * c16 + 1 < ntail) tail[rl][2 * c16 + 1] = h2f(t1) * h2f(psm[np + 2 * c16 + 1]);
-    wave_lds_fence();
-    if (c16 == 0) {
-        double sacc = (double) res;
-        for (int t = 0; t < ntail; t++) sacc += (double) tail[rl][t];
-        att[h * HD + d0] = (float) sacc;
-    }
+    vd_tail_store<false>(vd32_reduce(a0, a1), [&](int t) { return h2f(t ? t1 : t0) * h2f(psm[np + 2 * c16 + t]); }, tail[rl], c16, ntail, att + h * HD + d0);
 }
 
 // ---- (2 + 3) soft_max INSIDE the V.P launch: the contexts whose score row fits the LDS next to the V ring (ML <= AL_FUSED_MAX_ML) take two launches instead of three ----
@@ -249,7 +193,7 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
     // 16 waves: all of them do the soft_max; waves 0..3 own the V ring and the V.P chains (4 rows each), the others leave after the soft_max
     const int g = blockIdx.y, r2 = gridDim.z, h = g * r2 + blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool pv_wave = wave < 4;
-    const int n_kv = uniform_load_i32_(pos_dev) + 1, nv = n_kv & ~7, np = n_kv & ~31, nch = np >> 5, ntail = n_kv - np;
+    const int n_kv = uniform_load_i32(pos_dev) + 1, np = n_kv & ~31, nch = np >> 5, ntail = n_kv - np;
     const int c16 = lane & 15, sub = lane >> 4, rl = wave * 4 + sub, d0 = blockIdx.x * 16 + rl;
     float * ex = (float *) lds; float * gsum = ex + ML; uint16_t * p16 = (uint16_t *)(gsum + ML / 8);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *) lds;
@@ -257,7 +201,7 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
 
     // ---- the V ring: tile t = positions 512 t .. 512 t + 511 of this wave's 4 rows; lane l moves 16 bytes (8 positions) per row ----
     const int ntiles = (nch + 15) >> 4;
-    const char * vrow0 = (const char *)(v_cache + ((int64_t) g * HD + blockIdx.x * 16 + (wave & 3) * 4) * ML);
+    const char * vrow0 = (const char *) v_slot(v_cache, g, HD, blockIdx.x * 16 + (wave & 3) * 4, ML, 0);
     auto issue = [&](int t) {
         if (pv_wave && t < ntiles) {
             int p0 = t * AL_TILE + lane * 8;
@@ -276,7 +220,7 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
 #pragma unroll
     for (int t = 0; t < AL_NS - 1; t++) issue(t);
 
-    // ---- soft_max of head h (k_attn_long_softmax's arithmetic; 256 threads instead of 1024: the partition of the sums is the same) ----
+    // ---- soft_max of head h: the scores into LDS four at a time, then k_attn_long_softmax's steps ----
     const float * row = S + (int64_t) h * ML;
     float mx = -INFINITY;
     for (int i = tid * 4; i < n_kv; i += 4096) {                    // (ML % 8 == 0: a 16-byte load stays inside the row; the tail past n_kv is masked)
@@ -284,26 +228,7 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
         *(f32x4 *)(ex + i) = v;
         mx = fmaxf(mx, v.x); if (i + 1 < n_kv) mx = fmaxf(mx, v.y); if (i + 2 < n_kv) mx = fmaxf(mx, v.z); if (i + 3 < n_kv) mx = fmaxf(mx, v.w);
     }
-    mx = wave_max(mx);
-    if (lane == 0) red_f[wave] = mx;
-    __syncthreads();
-    mx = red_f[0];
-#pragma unroll
-    for (int w = 1; w < 16; w++) mx = fmaxf(mx, red_f[w]);
-    for (int gi = tid * 8; gi < nv; gi += 1024 * 8) {
-        const f32x4 s0 = *(const f32x4 *)(ex + gi), s1 = *(const f32x4 *)(ex + gi + 4);      // (16-byte LDS accesses: the 32-byte lane stride is 8-way conflicted for dwords)
-        float e[8] = { ggml_expf_poly(s0.x - mx), ggml_expf_poly(s0.y - mx), ggml_expf_poly(s0.z - mx), ggml_expf_poly(s0.w - mx),
-                       ggml_expf_poly(s1.x - mx), ggml_expf_poly(s1.y - mx), ggml_expf_poly(s1.z - mx), ggml_expf_poly(s1.w - mx) };
-        *(f32x4 *)(ex + gi) = f32x4{e[0], e[1], e[2], e[3]}; *(f32x4 *)(ex + gi + 4) = f32x4{e[4], e[5], e[6], e[7]};
-        gsum[gi >> 3] = soft_group8_sum(e);
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const double rinv = soft_total_rinv_groups(gsum, nv >> 3, ex, nv, n_kv, mx, n_kv >> 3, lane);
-        if (lane == 0) red_d[0] = rinv;
-    }
-    __syncthreads();
-    const float inv = (float) red_d[0];
+    const float inv = long_soft_max(mx, ex, gsum, n_kv, red_f, red_d, tid, lane, wave);
     for (int i = tid * 2; i < n_kv; i += 2048) {                    // the fp16 rounding src1 of V.P gets (exact in fp32 later)
         const uint32_t lo = f2h(ex[i] * inv), hi = i + 1 < n_kv ? f2h(ex[i + 1] * inv) : 0u;
         *(uint32_t *)(p16 + i) = lo | (hi << 16);
@@ -313,10 +238,7 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
 
     // ---- V.P: 32 serial chains per row, chunk by chunk ----
     float a0 = 0.0f, a1 = 0.0f;
-    auto step = [&](uint32_t vw, uint32_t pw) {
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "+v"(a0) : "v"(vw), "v"(pw));      // low halves
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(a1) : "v"(vw), "v"(pw));      // high halves
-    };
+    auto step = [&](uint32_t vw, uint32_t pw) { fma_mix_pair(a0, a1, vw, pw); };
     typedef __attribute__((address_space(3))) const uint32_t * lptr;
     const uint32_t * pp = (const uint32_t *) p16 + c16;
     for (int t = 0; t < ntiles; t++) {
@@ -333,18 +255,8 @@ __global__ void __launch_bounds__(1024) k_attn_long_softmax_pv(const int32_t * _
             for (int c = 0; c < nc; c++) step(vp[16 * c], pt[16 * c]);
         }
     }
-    const float res = al_vd32_reduce(a0, a1);
-    if (ntail) {                                                     // the n_kv mod 32 leftovers, one by one in double (products rounded to fp32 first)
-        const uint16_t * vr = v_cache + ((int64_t) g * HD + d0) * ML;
-        if (2 * c16 < ntail)     tail[rl][2 * c16]     = h2f(vr[np + 2 * c16])     * h2f(p16[np + 2 * c16]);
-        if (2 * c16 + 1 < ntail) tail[rl][2 * c16 + 1] = h2f(vr[np + 2 * c16 + 1]) * h2f(p16[np + 2 * c16 + 1]);
-    }
-    wave_lds_fence();
-    if (c16 == 0) {
-        double sacc = (double) res;
-        for (int t = 0; t < ntail; t++) sacc += (double) tail[rl][t];
-        att[h * HD + d0] = (float) sacc;
-    }
+    vd_tail_store<false>(vd32_reduce(a0, a1), [&](int t) { const int e = np + 2 * c16 + t; return h2f(*v_slot(v_cache, g, HD, d0, ML, e)) * h2f(p16[e]); },
+                         tail[rl], c16, ntail, att + h * HD + d0);
 }
 
 // CLLM_E_UNSUPPORTED -> the caller uses the single-launch kernels.  S: scratch of nh * ML * 6 bytes (fp32 scores + fp16 probabilities).
@@ -358,38 +270,37 @@ int launch_attn_long(hipStream_t st, const float * qkv, const int32_t * pos_dev,
     uint16_t * P16 = (uint16_t *)(S + (size_t) nh * ML);          // fp16 probabilities behind the fp32 scores
     const int cus = device_cu_count();
     int nsplit = 2 * cus / nkv; if (nsplit < 1) nsplit = 1; if (nsplit > 128) nsplit = 128;      // two 256-thread workgroups per CU
-#define SC(HD_, MODE_, R2_) hipLaunchKernelGGL((k_attn_long_scores<HD_, MODE_, R2_>), dim3(nsplit, nkv), dim3(256), 0, st, qkv, pos_dev, rope_cs, nh, nkv, scale, k_cache, v_cache, (int) ML, S, g_long_ts)
-#define SC2(HD_, R2_) do { if (mode == 0) SC(HD_, 0, R2_); else SC(HD_, 2, R2_); } while (0)
-#define SC3(HD_) do { if (r2 == 1) SC2(HD_, 1); else if (r2 == 2) SC2(HD_, 2); else if (r2 == 4) SC2(HD_, 4); else SC2(HD_, 8); } while (0)
-    if (hd == 128) SC3(128); else SC3(64);
-    LAUNCH_CHECK();
-    static const bool no_fuse = opt_int(OPT_CLLM_ATTN_LONG_3) == 1;      // (tools: the three-launch form at every length)
-    if (ML <= AL_FUSED_MAX_ML && ML % 32 == 0 && !no_fuse) {                       // soft_max inside the V.P launch
-        const size_t lds2 = (size_t) ML * 4 + (size_t)(ML / 8) * 4 + (size_t) ML * 2 + 4 * AL_NS * 4096;
-#define PV2(HD_) do { \
-            static uint64_t attr2 = 0; \
-            if (dev_flag_unset(attr2)) { HIP_TRY(hipFuncSetAttribute((const void *) k_attn_long_softmax_pv<HD_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); dev_flag_set(attr2); } \
-            hipLaunchKernelGGL((k_attn_long_softmax_pv<HD_>), dim3(HD_ / 16, nkv, r2), dim3(1024), lds2, st, pos_dev, nh, nkv, (const uint16_t *) v_cache, (int) ML, (const float *) S, att); } while (0)
-        if (hd == 128) PV2(128); else PV2(64);
-#undef PV2
+    int rc = with_head_dim(hd, [&](auto hd_c) { return with_rope_mode(mode, [&](auto mode_c) { return with_group(r2, [&](auto r2_c) -> int {
+        hipLaunchKernelGGL((k_attn_long_scores<decltype(hd_c)::value, decltype(mode_c)::value, decltype(r2_c)::value>), dim3(nsplit, nkv), dim3(256), 0, st,
+                           qkv, pos_dev, rope_cs, nh, nkv, scale, k_cache, v_cache, (int) ML, S, g_long_ts);
         LAUNCH_CHECK();
         return CLLM_OK;
+    }); }); });
+    if (rc) return rc;
+    static const bool no_fuse = opt_int(OPT_CLLM_ATTN_LONG_3) == 1;      // (tools: the three-launch form at every length)
+    if (ML <= AL_FUSED_MAX_ML && ML % 32 == 0 && !no_fuse) {                       // soft_max inside the V.P launch
+        const size_t lds2 = (size_t) ML * 4 + (size_t)(ML / 8) * 4 + (size_t) ML * 2 + 4 * AL_NS * 4096;      // (above 48 KB at every ML)
+        return with_head_dim(hd, [&](auto hd_c) -> int {
+            constexpr int HD = decltype(hd_c)::value;
+            static uint64_t attr2 = 0;
+            if (const int rc2 = lds_opt_in(k_attn_long_softmax_pv<HD>, attr2)) return rc2;
+            hipLaunchKernelGGL((k_attn_long_softmax_pv<HD>), dim3(HD / 16, nkv, r2), dim3(1024), lds2, st, pos_dev, nh, nkv, (const uint16_t *) v_cache, (int) ML, (const float *) S, att);
+            LAUNCH_CHECK();
+            return CLLM_OK;
+        });
     }
     static uint64_t attr = 0;
-    if (lds > 48 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_attn_long_softmax, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); dev_flag_set(attr); }
+    if (lds > 48 * 1024 && (rc = lds_opt_in(k_attn_long_softmax, attr))) return rc;
     hipLaunchKernelGGL(k_attn_long_softmax, dim3(nh), dim3(1024), lds, st, pos_dev, (int) ML, (const float *) S, P16);
     LAUNCH_CHECK();
     const size_t lds_pv = (size_t) ML * 2 + 16;
     if (lds_pv > 150 * 1024) return CLLM_E_UNSUPPORTED;
-#define PV(HD_) do { \
-        static uint64_t attr_pv = 0; \
-        if (lds_pv > 48 * 1024 && dev_flag_unset(attr_pv)) { HIP_TRY(hipFuncSetAttribute((const void *) k_attn_long_pv<HD_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); dev_flag_set(attr_pv); } \
-        hipLaunchKernelGGL((k_attn_long_pv<HD_>), dim3(HD_ / 16, nkv, r2), dim3(256), lds_pv, st, pos_dev, nh, nkv, (const uint16_t *) v_cache, (int) ML, (const uint16_t *) P16, att); } while (0)
-    if (hd == 128) PV(128); else PV(64);
-    LAUNCH_CHECK();
-#undef SC
-#undef SC2
-#undef SC3
-#undef PV
-    return CLLM_OK;
+    return with_head_dim(hd, [&](auto hd_c) -> int {
+        constexpr int HD = decltype(hd_c)::value;
+        static uint64_t attr_pv = 0;
+        if (lds_pv > 48 * 1024) if (const int rc3 = lds_opt_in(k_attn_long_pv<HD>, attr_pv)) return rc3;
+        hipLaunchKernelGGL((k_attn_long_pv<HD>), dim3(HD / 16, nkv, r2), dim3(256), lds_pv, st, pos_dev, nh, nkv, (const uint16_t *) v_cache, (int) ML, (const uint16_t *) P16, att);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    });
 }

@@ -354,6 +354,11 @@ __device__ __forceinline__ float uniform_load_f32(const float * p) {
     asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
     return v;
 }
+__device__ __forceinline__ int uniform_load_i32(const int32_t * p) {
+    int v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    return v;
+}
 
 // reductions inside groups of 8 consecutive lanes (one 32-element quant block = 8 lanes x 4 values)
 __device__ __forceinline__ float group8_max(float v) { v = fmaxf(v, dpp_f<DPP_QUAD_XOR1>(v)); v = fmaxf(v, dpp_f<DPP_QUAD_XOR2>(v)); return fmaxf(v, dpp_f<DPP_HALF_MIRROR>(v)); }
@@ -625,6 +630,28 @@ int device_cu_count();
 // process (chatllm.cpp's layer split over this module's devices) launches every kernel on each of them
 static inline bool dev_flag_unset(const uint64_t & m) { int d = 0; (void) hipGetDevice(&d); return !((m >> (d & 63)) & 1ull); }
 static inline void dev_flag_set(uint64_t & m) { int d = 0; (void) hipGetDevice(&d); m |= 1ull << (d & 63); }
+// raise a kernel's dynamic LDS limit, once per device (flag: a static uint64_t of the call site, one per kernel instantiation)
+template <class Kernel> static inline int lds_opt_in(Kernel kernel, uint64_t & flag, int bytes = 150 * 1024) {
+    if (dev_flag_unset(flag)) { HIP_TRY(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)); dev_flag_set(flag); }
+    return CLLM_OK;
+}
+// the single-token attention's compile-time parameters, in the idiom of with_tuned_type (types.h): f(std::integral_constant<int, V>()) for the value named.
+// Head sizes 64 / 128; RoPE pairing 0 (adjacent pairs) or 2 (NEOX halves: any other mode pairs NEOX-style, as in the general kernel); query heads per KV head 1 / 2 / 4 / 8.
+template <class F> static inline int with_head_dim(int hd, F && f) {
+    if (hd == 128) return f(std::integral_constant<int, 128>());
+    if (hd == 64)  return f(std::integral_constant<int, 64>());
+    return CLLM_E_UNSUPPORTED;
+}
+template <class F> static inline int with_rope_mode(int mode, F && f) {
+    return mode == 0 ? f(std::integral_constant<int, 0>()) : f(std::integral_constant<int, 2>());
+}
+template <class F> static inline int with_group(int r2, F && f) {
+    if (r2 == 1) return f(std::integral_constant<int, 1>());
+    if (r2 == 2) return f(std::integral_constant<int, 2>());
+    if (r2 == 4) return f(std::integral_constant<int, 4>());
+    if (r2 == 8) return f(std::integral_constant<int, 8>());
+    return CLLM_E_UNSUPPORTED;
+}
 // per-device scratch: a buffer allocated on one device must not serve launches on another (index = device id & 63)
 #define CLLM_DEV_SLOTS 64
 static inline int dev_slot() { int d = 0; (void) hipGetDevice(&d); return d & (CLLM_DEV_SLOTS - 1); }
@@ -683,14 +710,15 @@ int launch_gemv_rows32(hipStream_t st, int wtype, const void * W, int64_t K, int
 int gemv_team32_check();
 int launch_gemv_team32(hipStream_t st, int wtype, const void * W, int64_t K, int64_t nrows, int pro, const float * px, const float * pw, float eps, int epi, float * dst, const float * bias, const float * resid);
 int launch_mmvq_fused(hipStream_t st, int wtype, const void * W, int64_t K, int64_t nrows, int pro, const float * px, const float * pw, float eps, int epi, float * dst, const float * bias, const float * resid);
-int launch_attn_decode(hipStream_t st, const float * qkv, const int32_t * pos_dev, int nh, int nkv, int hd, const uint16_t * k_cache, const uint16_t * v_cache, int64_t ML, float * att);
 int launch_rope_table(hipStream_t st, const int32_t * pos_dev, int hd, float freq_base, float * cs);
-int launch_attn_dec_table(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, int nh, int nkv, int hd, int mode, uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * att);
 int launch_attn_long(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, int nh, int nkv, int hd, int mode, uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * S, float * att);
+// decode_fused.hip: RoPE + KV-cache write + attention of one token, by the first form that takes the shape: long-flash, long (both only with long_ctx: the context is above
+// attn_long_threshold() and `scratch` holds nh * ML * 6 bytes), the table kernel (rope_cs), the general kernel
+int launch_token_attention(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, float freq_base, bool long_ctx, int nh, int nkv, int hd, int mode,
+                           uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * scratch, size_t scratch_bytes, float * att);
 int launch_gemv_decode_id(hipStream_t st, int wtype, const void * W, size_t w_expert_bytes, int64_t K, int64_t nrows, const float * px, int64_t px_slot_stride,
                           const int32_t * ids, int n_slots, float * dst, int64_t dst_slot_stride, int epi = 0);
 int attn_long_threshold();      // decoder.hip: cached positions above which the split (3-launch) attention is used
-int launch_rope_kv_attn_decode(hipStream_t st, const float * qkv, const int32_t * pos_dev, int nh, int nkv, int hd, int mode, float freq_base, uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * att);
 int launch_argmax_partial(hipStream_t st, const float * logits, int n, float * part_v, int * part_i);
 int launch_argmax_final_next(hipStream_t st, const float * part_v, const int * part_i, int np, int32_t * tok_dev, int32_t * pos_dev, int32_t * out_ring, int32_t * counter,
                              int etype, const void * emb, size_t emb_nb1, int H, float * x_next, int hd, float freq_base, float * cs);

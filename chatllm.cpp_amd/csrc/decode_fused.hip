@@ -9,21 +9,10 @@
 // launch sequence that the runner captures once in a hipGraph.
 #include "common.h"
 #include "quant_dev.h"
-#include "q4k.h"
+#include "attn_token.h"
 #include "dequant.h"
 
 #include <math.h>
-
-// GGML_F32x8_REDUCE (simd-mappings.h:545-560) over the 32 accumulators of ggml_vec_dot_f16, held two per lane by 16 lanes (accumulator
-// a = 8 j + l in lane a / 2): x0 += x2, x1 += x3 (lanes c ^ 8); x0 += x1 (c ^ 4); lo + hi halves (c ^ 2); hadd, hadd (in-lane, c ^ 1)
-__device__ __forceinline__ float lane_xor4_ff(float v) { return __int_as_float(lane_xor4_i(__float_as_int(v))); }
-__device__ __forceinline__ float vd32_reduce(float a0, float a1) {
-    a0 = a0 + dpp_f<DPP_ROW_ROR8>(a0); a1 = a1 + dpp_f<DPP_ROW_ROR8>(a1);
-    a0 = a0 + lane_xor4_ff(a0);        a1 = a1 + lane_xor4_ff(a1);
-    a0 = a0 + dpp_f<DPP_QUAD_XOR2>(a0); a1 = a1 + dpp_f<DPP_QUAD_XOR2>(a1);
-    const float u = a0 + a1;
-    return u + dpp_f<DPP_QUAD_XOR1>(u);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Attention for one query token, one workgroup per query head.
@@ -83,9 +72,7 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
                 const int which = tid / half, i = tid % half, ic = rope_pair(mode, i, half).ic;
                 float c, s_;
                 rope_entry(pos, i, theta_scale, &c, &s_);
-                const float y0 = rope_rot_a(px0, px1, c, s_), y1 = rope_rot_b(px0, px1, c, s_);
-                float * o = which == 0 ? qs : knew;
-                o[ic] = h2f(f2h(y0)); o[ic + off] = h2f(f2h(y1));         // q: src1 of K.Q is rounded to fp16; k: the cache is fp16
+                token_rope_round(px0, px1, ic, off, c, s_, which == 0 ? qs : knew);
             } else if (tid < 2 * half + hd) vnew[tid - 2 * half] = h2f(f2h(pv));
         } else {
             float * cs = sc;                                            // scores are not live yet
@@ -93,20 +80,16 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
             __syncthreads();
             for (int t = tid; t < 2 * half; t += nthr) {
                 const int which = t / half, i = t % half, ic = rope_pair(mode, i, half).ic;
-                const float c = cs[2*i], s_ = cs[2*i + 1];
                 const float * x = which == 0 ? qh : kh;
-                const float x0 = x[ic], x1 = x[ic + off];
-                const float y0 = rope_rot_a(x0, x1, c, s_), y1 = rope_rot_b(x0, x1, c, s_);
-                float * o = which == 0 ? qs : knew;
-                o[ic] = h2f(f2h(y0)); o[ic + off] = h2f(f2h(y1));
+                token_rope_round(x[ic], x[ic + off], ic, off, cs[2*i], cs[2*i + 1], which == 0 ? qs : knew);
             }
             for (int d = tid; d < hd; d += nthr) vnew[d] = h2f(f2h(vh[d]));
         }
         __syncthreads();
         if (h % r2 == 0) {
             for (int d = tid; d < hd; d += nthr) {
-                k_cache[(int64_t) pos * KD + g * hd + d] = f2h(knew[d]);
-                v_cache[((int64_t) g * hd + d) * ML + pos] = f2h(vnew[d]);
+                *k_slot(k_cache, pos, KD, g, hd, d) = f2h(knew[d]);
+                *v_slot(v_cache, g, hd, d, ML, pos) = f2h(vnew[d]);
             }
         }
     } else {
@@ -116,7 +99,7 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
 
     // ---- (4) scores[i] = K[i] . q * scale, in ggml_vec_dot_f16's order ----
     for (int i0 = wave * 4 + sub; i0 < n_kv; i0 += nrg) {
-        const uint16_t * kr = k_cache + (int64_t) i0 * KD + g * hd;
+        const uint16_t * kr = k_slot(k_cache, i0, KD, g, hd, 0);
         const bool fr = ROPE && i0 == pos;
         float a0 = 0.0f, a1 = 0.0f;
         for (int e = 2 * c16; e < hnp; e += 32) {
@@ -134,11 +117,7 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
     // ---- (5) soft_max over sc[0..n_kv): same partition as k_soft_max (one wave, lane = groups of 8) ----
     float mx = -INFINITY;
     for (int i = tid; i < n_kv; i += nthr) mx = fmaxf(mx, sc[i]);
-    mx = wave_max(mx);
-    if (lane == 0) red_f[wave] = mx;
-    __syncthreads();
-    mx = red_f[0];
-    for (int w = 1; w < nw; w++) mx = fmaxf(mx, red_f[w]);
+    mx = block_max16(mx, red_f, lane, wave, [] { __syncthreads(); });       // (1024 threads: attn_launch)
     const int nv = n_kv & ~7;                  // (all threads compute the exponentials; the sum keeps the reference's order: see k_attn_dec)
     for (int i = tid; i < n_kv; i += nthr) sc[i] = i < nv ? ggml_expf_poly(sc[i] - mx) : libm_expf(sc[i] - mx);
     __syncthreads();
@@ -156,25 +135,15 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float * __restrict__
     float * tailp = sm + 3 * hd + (ML > hd ? ML : hd) + (wave * 4 + sub) * 32;
     const int np = n_kv & ~31, ntail = n_kv - np;
     for (int d0 = wave * 4 + sub; d0 < hd; d0 += nrg) {
-        const uint16_t * vr = v_cache + ((int64_t) g * hd + d0) * ML;
+        const uint16_t * vr = v_slot(v_cache, g, hd, d0, ML, 0);
         const float vfresh = ROPE ? vnew[d0] : 0.0f;
         float a0 = 0.0f, a1 = 0.0f;
         for (int e = 2 * c16; e < np; e += 32) {
             const float v0 = (ROPE && e == pos) ? vfresh : h2f(vr[e]), v1 = (ROPE && e + 1 == pos) ? vfresh : h2f(vr[e + 1]);
             a0 = __builtin_fmaf(v0, sc[e], a0); a1 = __builtin_fmaf(v1, sc[e + 1], a1);
         }
-        const float res = vd32_reduce(a0, a1);
-        for (int t = 0; t < 2; t++) {
-            const int e = np + 2 * c16 + t;
-            if (e < n_kv) tailp[2 * c16 + t] = ((ROPE && e == pos) ? vfresh : h2f(vr[e])) * sc[e];
-        }
-        wave_lds_fence();
-        if (c16 == 0) {
-            double s = (double) res;
-            for (int t = 0; t < ntail; t++) s += (double) tailp[t];
-            att[h * hd + d0] = (float) s;
-        }
-        wave_lds_fence();
+        vd_tail_store<true>(vd32_reduce(a0, a1), [&](int t) { const int e = np + 2 * c16 + t; return ((ROPE && e == pos) ? vfresh : h2f(vr[e])) * sc[e]; },
+                            tailp, c16, ntail, att + h * hd + d0);
     }
 }
 
@@ -194,18 +163,11 @@ int launch_rope_table(hipStream_t st, const int32_t * pos_dev, int hd, float fre
     return CLLM_OK;
 }
 
-__device__ __forceinline__ int uniform_load_i32(const int32_t * p) {
-    int v;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
-
 template <int HD, int MODE, int PARTS>      // MODE 0: adjacent pairs (GGML_ROPE_TYPE_NORMAL), 2: NEOX halves; PARTS: workgroups per head (each redoes RoPE, scores and
                                             // soft_max -- the same bits -- and takes 1 / PARTS of the V.P rows: one row per 16-lane group instead of two)
 __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qkv, const int32_t * __restrict__ pos_dev, const float * __restrict__ rope_cs,
                                                    int nh, int nkv, float scale, uint16_t * __restrict__ k_cache, uint16_t * __restrict__ v_cache,
                                                    int ML, float * __restrict__ att, unsigned long long * ts) {
-#define TS(k) do { if (ts && threadIdx.x == 0) ts[(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = wall_clock64(); } while (0)
     extern __shared__ __attribute__((aligned(16))) float sm[];       // [HD] q (fp16-rounded) | [HD] new k | [HD] new v | [n_kv] scores
     __shared__ float  red_f[16];
     __shared__ uint64_t etab_s[32];                                   // glibc's exp2f table for the soft_max's n mod 8 leftovers (see (5))
@@ -257,15 +219,13 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
     TS(0);
     // ---- (3) RoPE, fp16 rounding, cache write ----
     if (is_pair) {
-        const float y0 = rope_rot_a(px0, px1, pc, ps), y1 = rope_rot_b(px0, px1, pc, ps);
-        float * o = which == 0 ? qs : knew;
-        o[ic] = h2f(f2h(y0)); o[ic + off] = h2f(f2h(y1));             // q: src1 of K.Q is rounded to fp16; k: the cache is fp16
+        token_rope_round(px0, px1, ic, off, pc, ps, which == 0 ? qs : knew);
     } else if (is_v) vnew[tid - 2 * half] = h2f(f2h(px0));
     if (tid >= 992) etab_s[tid - 992] = et;
     lds_barrier();
     if (blockIdx.x == 0 && (PARTS == 1 || blockIdx.z == 0) && tid < HD) {
-        k_cache[(int64_t) pos * KD + g * HD + tid] = f2h(knew[tid]);
-        v_cache[((int64_t) g * HD + tid) * ML + pos] = f2h(vnew[tid]);
+        *k_slot(k_cache, pos, KD, g, HD, tid) = f2h(knew[tid]);
+        *v_slot(v_cache, g, HD, tid, ML, pos) = f2h(vnew[tid]);
     }
 
     TS(1);
@@ -323,12 +283,7 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
     // ---- (5) soft_max over sc[0..n_kv): same partition as k_soft_max (one wave, lane = groups of 8) ----
     float mx = -INFINITY;
     for (int i = tid; i < n_kv; i += 1024) mx = fmaxf(mx, sc[i]);
-    mx = wave_max(mx);
-    if (lane == 0) red_f[wave] = mx;
-    lds_barrier();
-    mx = red_f[0];
-#pragma unroll
-    for (int w = 1; w < 16; w++) mx = fmaxf(mx, red_f[w]);
+    mx = block_max16(mx, red_f, lane, wave, [] { lds_barrier(); });       // (not __syncthreads(): the V prefetches stay in flight)
     // every exponential is independent: all threads compute them (the groups of 8 through the AVX2 polynomial, the n_kv mod 8 leftovers through
     // expf, as ggml_vec_soft_max_f32 does); the total is one wave's (lane = groups of 8 -> double; leftovers last)
     const int nv = n_kv & ~7;
@@ -382,6 +337,8 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
             }
         }
         const float res = vd32_reduce(a0, a1);
+        // vd_tail_store<true>'s steps, written out (as are this kernel's row addresses, k_slot / v_slot with d = 0): through the helpers every form measured either grew this
+        // kernel's code (HD 64: +44 B) or took HD 128 from 60 to 66 VGPRs, and its size is on the decode critical path (above)
 #pragma unroll
         for (int t = 0; t < 2; t++) {
             const int e = np + 2 * c16 + t;
@@ -396,57 +353,62 @@ __global__ void __launch_bounds__(1024) k_attn_dec(const float * __restrict__ qk
         wave_lds_fence();
     }
     TS(4);
-#undef TS
 }
 
 // RoPE + KV-cache write + attention with the position's cos/sin table (launch_rope_table); CLLM_E_UNSUPPORTED -> use the general kernel
-int launch_attn_dec_table(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, int nh, int nkv, int hd, int mode,
-                          uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * att) {
+// THE dynamic LDS of the one-launch kernels: q | new k | new v | scores | leftover products of 64 lane groups.  general (k_attn_decode): its scores region also holds the
+// cos/sin table of head sizes above max_len
+static size_t attn_decode_lds_bytes(int hd, int64_t ML, bool general) {
+    return (size_t)(3 * hd + (general && ML < hd ? hd : ML)) * 4 + 64 * 32 * 4;
+}
+static int launch_attn_dec_table(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, int nh, int nkv, int hd, int mode,
+                                 uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * att) {
     if ((hd != 64 && hd != 128) || nh % nkv || ML % 8 || ML > (1 << 30) || g_attn_dbg) return CLLM_E_UNSUPPORTED;
-    const size_t lds = (size_t)(3 * hd + ML) * 4 + 64 * 32 * 4;      // q | new k | new v | scores | leftover products of 64 lane groups
+    const size_t lds = attn_decode_lds_bytes(hd, ML, false);
     if (lds > 150 * 1024) return CLLM_E_UNSUPPORTED;
     const float scale = 1.0f / sqrtf((float) hd);
-    const dim3 grid(nh / nkv, nkv, hd == 128 ? 2 : 1);
-#define GO(HD_, MODE_) do { \
-        static uint64_t attr = 0; \
-        if (lds > 48 * 1024 && dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) k_attn_dec<HD_, MODE_, (HD_ == 128 ? 2 : 1)>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); dev_flag_set(attr); } \
-        hipLaunchKernelGGL((k_attn_dec<HD_, MODE_, (HD_ == 128 ? 2 : 1)>), grid, dim3(1024), lds, st, qkv, pos_dev, rope_cs, nh, nkv, scale, k_cache, v_cache, (int) ML, att, g_attn_ts); } while (0)
-    if (hd == 128) { if (mode == 0) GO(128, 0); else GO(128, 2); }      // any other mode pairs NEOX-style, as in the general kernel
-    else           { if (mode == 0) GO(64, 0);  else GO(64, 2); }
-#undef GO
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    return with_head_dim(hd, [&](auto hd_c) { return with_rope_mode(mode, [&](auto mode_c) -> int {
+        constexpr int HD = decltype(hd_c)::value, PARTS = HD == 128 ? 2 : 1;
+        const auto kernel = k_attn_dec<HD, decltype(mode_c)::value, PARTS>;
+        static uint64_t attr = 0;
+        if (lds > 48 * 1024) if (const int rc = lds_opt_in(kernel, attr)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(nh / nkv, nkv, PARTS), dim3(1024), lds, st, qkv, pos_dev, rope_cs, nh, nkv, scale, k_cache, v_cache, (int) ML, att, g_attn_ts);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    }); });
 }
 
+// the general kernel.  rope: RoPE + KV-cache write + attention in one launch (qkv holds the UN-rotated projections)
 static int attn_launch(hipStream_t st, bool rope, const float * qkv, const int32_t * pos_dev, int nh, int nkv, int hd, uint16_t * k_cache, uint16_t * v_cache,
                        int64_t ML, float * att, int mode, float freq_base) {
     if (hd % 8 || (ML % 8) || nh % nkv) FAIL(CLLM_E_UNSUPPORTED, "attn_decode: head_dim and max_len must be multiples of 8");
-    const size_t lds = (size_t)(3 * hd + (ML > hd ? ML : hd)) * 4 + 64 * 32 * 4;      // q | new k | new v | scores (reused for the cos/sin table) | leftover products
+    const size_t lds = attn_decode_lds_bytes(hd, ML, true);
     if (lds > 150 * 1024) FAIL(CLLM_E_UNSUPPORTED, "attn_decode: max_len %lld does not fit LDS", (long long) ML);
-    static uint64_t attr0 = 0, attr1 = 0;
-    if (lds > 48 * 1024) {
-        if (!rope && dev_flag_unset(attr0)) { HIP_TRY(hipFuncSetAttribute((const void *) k_attn_decode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); dev_flag_set(attr0); }
-        if (rope && dev_flag_unset(attr1))  { HIP_TRY(hipFuncSetAttribute((const void *) k_attn_decode<true>,  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); dev_flag_set(attr1); }
-    }
     const float scale = 1.0f / sqrtf((float) hd), theta_scale = powf(freq_base, -2.0f / hd);
-    if (rope) hipLaunchKernelGGL(k_attn_decode<true>,  dim3(nh), dim3(1024), lds, st, qkv, pos_dev, nh, nkv, hd, scale, k_cache, v_cache, ML, att, g_attn_dbg, mode, theta_scale);
-    else      hipLaunchKernelGGL(k_attn_decode<false>, dim3(nh), dim3(1024), lds, st, qkv, pos_dev, nh, nkv, hd, scale, k_cache, v_cache, ML, att, g_attn_dbg, mode, theta_scale);
-    LAUNCH_CHECK();
-    return CLLM_OK;
-}
-int launch_attn_decode(hipStream_t st, const float * qkv, const int32_t * pos_dev, int nh, int nkv, int hd, const uint16_t * k_cache,
-                       const uint16_t * v_cache, int64_t ML, float * att) {
-    return attn_launch(st, false, qkv, pos_dev, nh, nkv, hd, (uint16_t *) k_cache, (uint16_t *) v_cache, ML, att, 0, 10000.0f);
-}
-// RoPE + KV-cache write + attention in one launch (qkv holds the UN-rotated projections)
-int launch_rope_kv_attn_decode(hipStream_t st, const float * qkv, const int32_t * pos_dev, int nh, int nkv, int hd, int mode, float freq_base,
-                               uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * att) {
-    return attn_launch(st, true, qkv, pos_dev, nh, nkv, hd, k_cache, v_cache, ML, att, mode, freq_base);
+    const auto go = [&](auto rope_c) -> int {
+        const auto kernel = k_attn_decode<decltype(rope_c)::value>;
+        static uint64_t attr = 0;
+        if (lds > 48 * 1024) if (const int rc = lds_opt_in(kernel, attr)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(nh), dim3(1024), lds, st, qkv, pos_dev, nh, nkv, hd, scale, k_cache, v_cache, ML, att, g_attn_dbg, mode, theta_scale);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    };
+    return rope ? go(std::true_type()) : go(std::false_type());
 }
 extern "C" int cllm_op_attn_decode(void * stream, const float * q, const int32_t * pos_dev, int n_head, int n_kv_head, int head_dim,
                                    const void * k_cache, const void * v_cache, int64_t max_len, float * out) {
     if (!q || !pos_dev || !k_cache || !v_cache || !out || n_head <= 0 || n_kv_head <= 0 || head_dim <= 0) FAIL(CLLM_E_INVALID, "attn_decode: arguments");
-    return launch_attn_decode((hipStream_t) stream, q, pos_dev, n_head, n_kv_head, head_dim, (const uint16_t *) k_cache, (const uint16_t *) v_cache, max_len, out);
+    return attn_launch((hipStream_t) stream, false, q, pos_dev, n_head, n_kv_head, head_dim, (uint16_t *) k_cache, (uint16_t *) v_cache, max_len, out, 0, 10000.0f);
+}
+// RoPE + KV-cache write + attention of one token by the first form that takes the shape (common.h)
+int launch_token_attention(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, float freq_base, bool long_ctx, int nh, int nkv, int hd, int mode,
+                           uint16_t * k_cache, uint16_t * v_cache, int64_t ML, float * scratch, size_t scratch_bytes, float * att) {
+    int rc = CLLM_E_UNSUPPORTED;
+    if (rope_cs && long_ctx) rc = launch_attn_long_flash(st, qkv, pos_dev, rope_cs, nh, nkv, hd, mode, k_cache, v_cache, ML, scratch, scratch_bytes, att);
+    if (rc == CLLM_E_UNSUPPORTED && rope_cs && long_ctx) rc = launch_attn_long(st, qkv, pos_dev, rope_cs, nh, nkv, hd, mode, k_cache, v_cache, ML, scratch, att);
+    if (rc == CLLM_E_UNSUPPORTED && rope_cs) rc = launch_attn_dec_table(st, qkv, pos_dev, rope_cs, nh, nkv, hd, mode, k_cache, v_cache, ML, att);
+    if (rc == CLLM_E_UNSUPPORTED) rc = attn_launch(st, true, qkv, pos_dev, nh, nkv, hd, k_cache, v_cache, ML, att, mode, freq_base);
+    return rc;
 }
 
 // The whole single-token attention block between the q/k/v projections and o_proj as ONE call (1 launch up to the long-context
@@ -459,7 +421,7 @@ extern "C" int cllm_op_rope_table(void * stream, const int32_t * pos_dev, int he
 extern "C" int cllm_attn_decode_supported(int n_head, int n_kv_head, int head_dim, int64_t max_len) {       // the shapes attn_launch() takes
     if (n_head <= 0 || n_kv_head <= 0 || head_dim <= 0 || max_len <= 0) return 0;
     if (head_dim % 8 || max_len % 8 || n_head % n_kv_head) return 0;
-    return (size_t)(3 * head_dim + (max_len > head_dim ? max_len : head_dim)) * 4 <= 150 * 1024;
+    return attn_decode_lds_bytes(head_dim, max_len, true) <= 150 * 1024;
 }
 extern "C" size_t cllm_attn_decode_wsize(int64_t n_kv, int n_head, int64_t max_len) {
     return n_kv > attn_long_threshold() ? (size_t) n_head * (size_t) max_len * 6 : 0;
@@ -470,18 +432,9 @@ extern "C" int cllm_op_rope_kv_attn_decode(void * stream, const float * qkv, con
     if (!qkv || !pos_dev || !k_cache || !v_cache || !out || n_head <= 0 || n_kv_head <= 0 || head_dim <= 0 || n_kv <= 0 || n_kv > max_len)
         FAIL(CLLM_E_INVALID, "rope_kv_attn_decode: arguments");
     if (rope_mode != 0 && rope_mode != 2) FAIL(CLLM_E_UNSUPPORTED, "rope_kv_attn_decode: rope mode %d", rope_mode);
-    hipStream_t st = (hipStream_t) stream;
-    int rc = CLLM_E_UNSUPPORTED;
     const size_t need = cllm_attn_decode_wsize(n_kv, n_head, max_len);
-    if (rope_cs && need && wdata && wsize >= need)
-        rc = launch_attn_long_flash(st, qkv, pos_dev, rope_cs, n_head, n_kv_head, head_dim, rope_mode, (uint16_t *) k_cache, (uint16_t *) v_cache, max_len, (float *) wdata, wsize, out);
-    if (rc == CLLM_E_UNSUPPORTED && rope_cs && need && wdata && wsize >= need)
-        rc = launch_attn_long(st, qkv, pos_dev, rope_cs, n_head, n_kv_head, head_dim, rope_mode, (uint16_t *) k_cache, (uint16_t *) v_cache, max_len, (float *) wdata, out);
-    if (rc == CLLM_E_UNSUPPORTED && rope_cs)
-        rc = launch_attn_dec_table(st, qkv, pos_dev, rope_cs, n_head, n_kv_head, head_dim, rope_mode, (uint16_t *) k_cache, (uint16_t *) v_cache, max_len, out);
-    if (rc == CLLM_E_UNSUPPORTED)
-        rc = launch_rope_kv_attn_decode(st, qkv, pos_dev, n_head, n_kv_head, head_dim, rope_mode, freq_base, (uint16_t *) k_cache, (uint16_t *) v_cache, max_len, out);
-    return rc;
+    return launch_token_attention((hipStream_t) stream, qkv, pos_dev, rope_cs, freq_base, need && wdata && wsize >= need, n_head, n_kv_head, head_dim, rope_mode,
+                                  (uint16_t *) k_cache, (uint16_t *) v_cache, max_len, (float *) wdata, wsize, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

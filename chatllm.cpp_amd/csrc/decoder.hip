@@ -571,12 +571,8 @@ static int decode_step_fused(cllm_llama * m, bool sample, bool long_ctx, bool he
     for (int il = 0; il < c.n_layer; il++) {
         llama_layer & L = m->layers[il];
         TRY(norm_gemv(L.wqkv, QD + 2*KD, (const float *) L.attn_norm.data, 0, m->qkv, c.qkv_bias ? (const float *) L.bqkv.data : nullptr));
-        int arc = CLLM_E_UNSUPPORTED;
-        if (cs_table && long_ctx) arc = launch_attn_long_flash(st, m->qkv, m->pos_dev, rope_cs, m->nh, m->nkv, (int) hd, c.rope_mode, L.k_cache, L.v_cache, ML, m->scores, m->scores_elems * 4, m->att);
-        if (arc == CLLM_E_UNSUPPORTED && cs_table && long_ctx) arc = launch_attn_long(st, m->qkv, m->pos_dev, rope_cs, m->nh, m->nkv, (int) hd, c.rope_mode, L.k_cache, L.v_cache, ML, m->scores, m->att);
-        if (arc == CLLM_E_UNSUPPORTED && cs_table) arc = launch_attn_dec_table(st, m->qkv, m->pos_dev, rope_cs, m->nh, m->nkv, (int) hd, c.rope_mode, L.k_cache, L.v_cache, ML, m->att);
-        if (arc == CLLM_E_UNSUPPORTED) arc = launch_rope_kv_attn_decode(st, m->qkv, m->pos_dev, m->nh, m->nkv, (int) hd, c.rope_mode, c.rope_theta, L.k_cache, L.v_cache, ML, m->att);
-        TRY(arc);
+        TRY(launch_token_attention(st, m->qkv, m->pos_dev, cs_table ? rope_cs : nullptr, c.rope_theta, cs_table && long_ctx, m->nh, m->nkv, (int) hd, c.rope_mode,
+                                   L.k_cache, L.v_cache, ML, m->scores, m->scores_elems * 4, m->att));
         if (!tp) TRY(launch_mmvq_fused(st, L.wo.type, L.wo.data, QD, H, 2, m->att, nullptr, 0.0f, 0, xc, nullptr, xc));          // x = o + x
         else if (fused_ar) {
             const int rc = launch_gemv_decode_tp_scatter(st, L.wo.type, L.wo.data, QD, H, 2, m->att, fctx, 2 * il);

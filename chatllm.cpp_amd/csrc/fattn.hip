@@ -21,7 +21,7 @@
 // A workgroup is NW waves x 32 query rows over one (kv head | head); K/V tiles of 64 positions are staged through LDS by all
 // waves.  Decode (few rows): the r heads of a GQA group are packed as rows of one tile (R = r) so K/V are read once per
 // group, NW = 1, and the positions are split over gridDim.x workgroups whose partial (m, l, O) are merged by k_fattn_merge.
-#include "common.h"
+#include "attn_token.h"      // k_slot, v_slot: the cache layouts k_rope_kv_prep writes
 #include <stdlib.h>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -59,22 +59,6 @@ __device__ __forceinline__ float fa_pair_max(float x) {
 __device__ __forceinline__ float fa_pair_sum(float x) {
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// 8 consecutive elements e0 .. e0 + 7 (e0 % 8 == 0) of a Q8_0 row as fp16(d * q); blocks are 34 bytes, so 2-byte loads
-__device__ __forceinline__ u32x4 fa_q8_8(const char * row, int e0) {
-    const char * p = row + (e0 >> 5) * 34;
-    const float d = h2f(*(const uint16_t *) p);
-    const uint16_t * qs = (const uint16_t *)(p + 2 + (e0 & 31));
-    u32x4 out;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t w = qs[i];
-        const _Float16 lo = (_Float16)(d * (float)(int8_t)(w & 0xff)), hi = (_Float16)(d * (float)(int8_t)(w >> 8));
-        uint16_t a, b; __builtin_memcpy(&a, &lo, 2); __builtin_memcpy(&b, &hi, 2);
-        out[i] = (uint32_t) a | ((uint32_t) b << 16);
-    }
-    return out;
 }
 
 template <int D, int KVT, int VL, int MASK, int NW>
@@ -539,9 +523,9 @@ __global__ void __launch_bounds__(HD) k_rope_kv_prep(const float * __restrict__ 
         const float x0 = x[ic], x1 = x[ic + off], c = rope_cs[2 * tid], sn = rope_cs[2 * tid + 1];
         const float y0 = rope_rot_a(x0, x1, c, sn), y1 = rope_rot_b(x0, x1, c, sn);
         if (is_q) { qrot[blk * HD + ic] = y0; qrot[blk * HD + ic + off] = y1; }
-        else { k_cache[(int64_t) pos * KD + g * HD + ic] = f2h(y0); k_cache[(int64_t) pos * KD + g * HD + ic + off] = f2h(y1); }
+        else { *k_slot(k_cache, pos, KD, g, HD, ic) = f2h(y0); *k_slot(k_cache, pos, KD, g, HD, ic + off) = f2h(y1); }
     }
-    if (!is_q) v_cache[((int64_t) g * HD + tid) * ML + pos] = f2h(qkv[QD + KD + g * HD + tid]);
+    if (!is_q) *v_slot(v_cache, g, HD, tid, ML, pos) = f2h(qkv[QD + KD + g * HD + tid]);
 }
 
 int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * pos_dev, const float * rope_cs, int nh, int nkv, int hd, int mode,
@@ -556,11 +540,13 @@ int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * po
     if (max_splits > FA_MAX_SPLITS) max_splits = FA_MAX_SPLITS;
     if (max_splits < 4) return CLLM_E_UNSUPPORTED;
     float * qrot = S;
-    if (hd == 128) { if (mode == 0) hipLaunchKernelGGL((k_rope_kv_prep<128, 0>), dim3(nh + nkv), dim3(128), 0, st, qkv, pos_dev, rope_cs, nh, nkv, k_cache, v_cache, (int) ML, qrot);
-                     else           hipLaunchKernelGGL((k_rope_kv_prep<128, 2>), dim3(nh + nkv), dim3(128), 0, st, qkv, pos_dev, rope_cs, nh, nkv, k_cache, v_cache, (int) ML, qrot); }
-    else           { if (mode == 0) hipLaunchKernelGGL((k_rope_kv_prep<64, 0>),  dim3(nh + nkv), dim3(64),  0, st, qkv, pos_dev, rope_cs, nh, nkv, k_cache, v_cache, (int) ML, qrot);
-                     else           hipLaunchKernelGGL((k_rope_kv_prep<64, 2>),  dim3(nh + nkv), dim3(64),  0, st, qkv, pos_dev, rope_cs, nh, nkv, k_cache, v_cache, (int) ML, qrot); }
-    LAUNCH_CHECK();
+    const int rc = with_head_dim(hd, [&](auto hd_c) { return with_rope_mode(mode, [&](auto mode_c) -> int {
+        constexpr int HD = decltype(hd_c)::value;
+        hipLaunchKernelGGL((k_rope_kv_prep<HD, decltype(mode_c)::value>), dim3(nh + nkv), dim3(HD), 0, st, qkv, pos_dev, rope_cs, nh, nkv, k_cache, v_cache, (int) ML, qrot);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    }); });
+    if (rc) return rc;
     const int KD = nkv * hd;
     fattn_args a;
     a.q = (const char *) qrot; a.q_nb1 = (int64_t) nh * hd * 4; a.q_nb2 = (int64_t) hd * 4; a.q_nb3 = a.q_nb1;
@@ -576,11 +562,12 @@ int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * po
     a.chunk = per * 64; a.splits = (tiles + per - 1) / per;
     const size_t lds = 64 * (size_t) hd * 2 + (size_t) hd * FA_VSTR;
     const dim3 grid((unsigned) a.splits, (unsigned) nkv, 1);
-    if (hd == 128) hipLaunchKernelGGL((k_fattn<128, CLLM_TYPE_F16, 1, 0, 4>), grid, dim3(256), lds, st, a);
-    else           hipLaunchKernelGGL((k_fattn<64,  CLLM_TYPE_F16, 1, 0, 4>), grid, dim3(256), lds, st, a);
-    LAUNCH_CHECK();
-    if (hd == 128) hipLaunchKernelGGL((k_fattn_merge<128>), dim3(1, (unsigned) nh, 1), dim3(1024), 0, st, a);
-    else           hipLaunchKernelGGL((k_fattn_merge<64>),  dim3(1, (unsigned) nh, 1), dim3(1024), 0, st, a);
-    LAUNCH_CHECK();
-    return CLLM_OK;
+    return with_head_dim(hd, [&](auto hd_c) -> int {
+        constexpr int HD = decltype(hd_c)::value;
+        hipLaunchKernelGGL((k_fattn<HD, CLLM_TYPE_F16, 1, 0, 4>), grid, dim3(256), lds, st, a);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL((k_fattn_merge<HD>), dim3(1, (unsigned) nh, 1), dim3(1024), 0, st, a);
+        LAUNCH_CHECK();
+        return CLLM_OK;
+    });
 }

@@ -141,8 +141,7 @@ __global__ void __launch_bounds__(1024) k_gemv_dec(const float * __restrict__ px
     float * const             probs_out = xout;                                            // EPI 5
     const int                 act_slot_stride = px_slot_stride, out_slot_stride = dst_slot_stride;      // MOE / EPI 3 / EPI 5: per-slot strides
     if constexpr (MOE && EPI != 5) {
-        int e;
-        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(e) : "s"(moe_ids + blockIdx.y) : "memory");
+        const int e = uniform_load_i32(moe_ids + blockIdx.y);
         W += (unsigned long long)(unsigned) e * w_expert_bytes;
         px += (long) blockIdx.y * act_slot_stride; dst += (long) blockIdx.y * out_slot_stride;
     }

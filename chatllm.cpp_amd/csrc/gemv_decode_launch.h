@@ -65,10 +65,7 @@ struct gemv_dec_args {
 template <int FMT, int PRO, int EPI, int NPRE, bool MOE = false, bool FREE = false>
 static int gemv_dec_launch(hipStream_t st, const gemv_dec_plan & p, const gemv_dec_args & a) {
     static uint64_t attr = 0;
-    if (p.lds > 64 * 1024 && dev_flag_unset(attr)) {
-        HIP_TRY(hipFuncSetAttribute((const void *) k_gemv_dec<FMT, PRO, EPI, NPRE, MOE, FREE>, hipFuncAttributeMaxDynamicSharedMemorySize, K_GEMV_DEC_MAX_DYN_LDS));
-        dev_flag_set(attr);
-    }
+    if (p.lds > 64 * 1024) if (const int rc = lds_opt_in(k_gemv_dec<FMT, PRO, EPI, NPRE, MOE, FREE>, attr, K_GEMV_DEC_MAX_DYN_LDS)) return rc;
     hipLaunchKernelGGL((k_gemv_dec<FMT, PRO, EPI, NPRE, MOE, FREE>), dim3(p.grid_x, p.grid_y), dim3(1024), p.lds, st, a.px, a.pw, a.padd, a.W, p.nblk, p.kfull, p.nrem, a.eps,
                        a.dst, a.xout, a.bias, a.resid, a.ts, a.ids, a.w_expert_bytes, a.px_slot_stride, a.dst_slot_stride);
     LAUNCH_CHECK();

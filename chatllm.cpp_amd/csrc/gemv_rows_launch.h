@@ -31,7 +31,7 @@ static inline size_t gemv_row_lds(int wtype, int64_t K, bool c0_plane, size_t st
 template <auto KERNEL, int MAX_DYN_LDS, class... Args>
 static int gemv_row_launch(hipStream_t st, int grid, size_t lds, Args... args) {
     static uint64_t attr = 0;
-    if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS)); dev_flag_set(attr); }
+    if (const int rc = lds_opt_in(KERNEL, attr, MAX_DYN_LDS)) return rc;
     hipLaunchKernelGGL(KERNEL, dim3((unsigned) grid), dim3(1024), lds, st, args...);
     LAUNCH_CHECK();
     return CLLM_OK;

@@ -42,8 +42,7 @@ template <> struct ld8<float> {
 //      ONE 8-lane accumulator per output element over steps of 8, then hsum.
 // Mapping: VD -- 16 lanes per src0 row, lane c carries accumulators 2c and 2c + 1; T8 -- 8 lanes per row, lane l carries accumulator l.
 // Four src1 columns share every src0 load.  (The many-column prefill contractions run on the matrix cores, mma_f16.hip: tolerance tier.)
-#include "q4k.h"        // lane_xor4_i, DPP_ROW_ROR8
-__device__ __forceinline__ float lane_xor4_f(float v) { return __int_as_float(lane_xor4_i(__float_as_int(v))); }
+#include "attn_token.h"        // vd32_reduce: the tree the attention kernels take too
 
 struct mmf_cols { const char * xc[4]; float * dc[4]; bool ok[4]; };
 __device__ __forceinline__ void mmf_columns(const tview & x, const tview & d, int64_t c0, int64_t ncol, int64_t i02, int64_t i03, int64_t r2, int64_t r3, mmf_cols & C) {
@@ -83,13 +82,7 @@ __global__ void __launch_bounds__(256) k_mul_mat_f_vd(tview w, tview x, tview d)
         }
 #pragma unroll
         for (int c = 0; c < 4; c++) {
-            // accumulator a = 8j + l sits in lane (a / 2): x0 += x2, x1 += x3 (lanes c ^ 8); x0 += x1 (c ^ 4); lo + hi (c ^ 2); hadd, hadd
-            float v0 = a0[c], v1 = a1[c];
-            v0 = v0 + dpp_f<DPP_ROW_ROR8>(v0); v1 = v1 + dpp_f<DPP_ROW_ROR8>(v1);
-            v0 = v0 + lane_xor4_f(v0);         v1 = v1 + lane_xor4_f(v1);
-            v0 = v0 + dpp_f<DPP_QUAD_XOR2>(v0); v1 = v1 + dpp_f<DPP_QUAD_XOR2>(v1);
-            float u = v0 + v1;
-            u = u + dpp_f<DPP_QUAD_XOR1>(u);
+            float u = vd32_reduce(a0[c], a1[c]);
             if (active && c16 == 0 && C.ok[c]) {
                 if (sizeof(T) == 2) {
                     double s = (double) u;

@@ -31,7 +31,7 @@ template <void (*KERNEL)(const mm_tile_args)>
 static int mm_tile_launch(int64_t tiles_m, int64_t tiles_n, int threads, int lds, hipStream_t st, const mm_tile_args & a, const char * name) {
     static uint64_t attr = 0;
     if (tiles_m * tiles_n > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "%s: too many tiles", name);
-    if (dev_flag_unset(attr)) { HIP_TRY(hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); dev_flag_set(attr); }
+    if (const int rc = lds_opt_in(KERNEL, attr, lds)) return rc;
     hipLaunchKernelGGL(KERNEL, dim3((unsigned)(tiles_m * tiles_n)), dim3(threads), lds, st, a);
     LAUNCH_CHECK();
     return CLLM_OK;

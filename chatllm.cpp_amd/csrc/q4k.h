@@ -26,6 +26,7 @@ __device__ __forceinline__ int lane_xor4_i(int v) {
     const int r = __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHL4, 0xf, 0x5, false);      // lanes 0-3, 8-11 of a row <- lane + 4
     return __builtin_amdgcn_update_dpp(r, v, DPP_ROW_SHR4, 0xf, 0xA, false);             // lanes 4-7, 12-15        <- lane - 4
 }
+__device__ __forceinline__ float lane_xor4_f(float v) { return __int_as_float(lane_xor4_i(__float_as_int(v))); }
 
 // ---- chain records: per wave, 8 pairs of super-blocks x 12 slots x {x_i, d_i, x_i+1, d_i+1} floats (+ 64 B so that the idle lanes
 //      12..15 of a row read inside the buffer) ----

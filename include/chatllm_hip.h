@@ -287,7 +287,9 @@ CLLM_API int cllm_op_attn_decode(void * stream, const float * q, const int32_t *
  * rope_cs: cllm_op_rope_table() of pos_dev (NULL: computed in the kernel from freq_base); rope_mode 0 (pairs i,i+1) or 2 (NEOX),
  * n_dims == head_dim, no YaRN / frequency factors (ggml_compute_forward_rope_flt, ops.cpp:5589-5865); n_kv: host copy of the cached
  * length, used only to pick the kernel; wdata: cllm_attn_decode_wsize(n_kv, ..) bytes (may be NULL when that is 0).
- * Bit-identical to the unfused nodes. */
+ * Bit-identical to the unfused nodes.
+ * cllm_attn_decode_supported(): 1 exactly where the one-launch kernel can launch -- head_dim and max_len multiples of 8, n_head a multiple of n_kv_head, and its
+ * whole LDS footprint within 150 KB: (3 * head_dim + max(max_len, head_dim)) floats AND the 64 x 32 floats of leftover slots (head_dim 128: max_len <= 35968). */
 CLLM_API int    cllm_op_rope_table(void * stream, const int32_t * pos_dev, int head_dim, float freq_base, float * cs /* head_dim floats */);
 CLLM_API int    cllm_attn_decode_supported(int n_head, int n_kv_head, int head_dim, int64_t max_len);
 CLLM_API size_t cllm_attn_decode_wsize(int64_t n_kv, int n_head, int64_t max_len);

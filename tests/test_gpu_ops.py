@@ -864,6 +864,7 @@ def test_attention_composite(gpu, qlen, n_past):
     (128, 32, 8, 16384, 12345, 0, True),
     (64, 4, 2, 64, 11, 0, True), (64, 4, 2, 64, 63, 2, True),
     (128, 32, 8, 1024, 100, 0, False),      # no table: the general kernel computes cos/sin itself
+    (128, 2, 1, 35968, 39, 0, True), (128, 2, 1, 35968, 39, 0, False),      # the largest max_len cllm_attn_decode_supported() admits: exactly 150 KB of dynamic LDS, both one-launch kernels
     (96, 6, 2, 256, 40, 2, True)])          # head size the compact kernels do not take -> general kernel
 def test_rope_kv_attn_decode_equals_the_node_sequence(gpu, hd, nh, nkv, ML, n_past, mode, table):
     ops, T = gpu.ops, gpu.Tensor
@@ -942,6 +943,10 @@ def test_rope_kv_attn_decode_rejects_what_it_cannot_do(gpu):
     assert L.cllm_attn_decode_supported(32, 8, 128, 1024) == 1
     assert L.cllm_attn_decode_supported(32, 8, 128, 1 << 17) == 0          # scores of one head no longer fit the LDS
     assert L.cllm_attn_decode_supported(32, 5, 128, 1024) == 0
+    # the footprint counts the leftover slots: 150 KB - 64 x 32 x 4 B = 36352 floats = 3 x 128 + 35968
+    assert L.cllm_attn_decode_supported(32, 8, 128, 35968) == 1
+    assert L.cllm_attn_decode_supported(32, 8, 128, 35976) == 0
+    assert L.cllm_attn_decode_supported(32, 8, 128, 36864) == 0          # (3 x 128 + 36864) x 4 alone would fit: the kernel cannot launch
     assert L.cllm_attn_decode_wsize(100, 32, 2048) == 0 and L.cllm_attn_decode_wsize(512, 32, 2048) == 0 and L.cllm_attn_decode_wsize(513, 32, 2048) == 32 * 2048 * 6   # (CLLM_ATTN_LONG, default 512)
     x = T.from_numpy(np.zeros(4096, np.float32)); pos = T.from_numpy(np.zeros(1, np.int32)); kc = T.from_numpy(np.zeros((64, 256), np.float16))
     rc = L.cllm_op_rope_kv_attn_decode(None, x.data_ptr(), pos.data_ptr(), None, 1e4, 1, 4, 2, 128, 1, kc.data_ptr(), kc.data_ptr(), 64, x.data_ptr(), None, 0)
