@@ -337,6 +337,142 @@ __device__ __forceinline__ float norm_variance(double V, int64_t n, float mean, 
     return nm_variance(V, n);
 }
 
+// ---- L2_NORM: the sum of squares is RMS_NORM's (rms_block_sumsq_1024, rms_serial_sumsq: the same terms in the same two orders); the interval test and the float steps
+// are nm_l2_order_safe and nm_l2_scale of norm_order.h.  Two shapes.
+// A 1024-thread workgroup per row: the branch is uniform over the workgroup (every thread holds the same `sum`); x must still hold the row, which is what the barriers
+// are for, as in rms_scale.  `part`: the 16 doubles rms_block_sumsq_1024 was given.
+__device__ __forceinline__ float l2_block_scale(double sum, int64_t n, float eps, const float * x, double * part) {
+    if (!nm_l2_order_safe(sum, n)) {
+        __syncthreads();                                        // every thread has read part[0..15]
+        if (threadIdx.x < 64) { const double ss = rms_serial_sumsq<false>(x, nullptr, n); if (threadIdx.x == 0) part[0] = ss; }
+        __syncthreads();
+        sum = part[0];
+    }
+    return nm_l2_scale(sum, eps);
+}
+// One WAVE per row of at most 512 elements, the row in registers (two float4 per lane and one leftover).  The outcome of the interval test differs from wave to wave, so
+// nothing here may hold a barrier or hand anything over through LDS: the wave whose row fails the test runs the serial chain itself (rms_serial_sumsq works per wave:
+// the lanes of ONE wave, v_readlane), and rms_scale / l2_block_scale must not be called from this shape.
+struct l2_wave_row { f32x4 v0, v1; float t; };
+__device__ __forceinline__ l2_wave_row l2_wave_load(const float * x, int64_t n, bool aligned) {
+    const int lane = threadIdx.x & 63;
+    const int nq = (int)(n >> 2);
+    l2_wave_row r = { f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}, 0.0f };
+    if (lane < nq)      r.v0 = rms_load4(x, lane, aligned);
+    if (lane + 64 < nq) r.v1 = rms_load4(x, lane + 64, aligned);
+    if (4 * nq + lane < n) r.t = x[4 * nq + lane];
+    return r;
+}
+__device__ __forceinline__ float l2_wave_scale(const l2_wave_row & r, int64_t n, float eps, const float * x) {
+    // (elements beyond the row are +0: their squares add +0 to a sum that starts from +0, which changes nothing)
+    double sum = 0.0;
+    sum += (double)(r.v0.x * r.v0.x); sum += (double)(r.v0.y * r.v0.y); sum += (double)(r.v0.z * r.v0.z); sum += (double)(r.v0.w * r.v0.w);
+    sum += (double)(r.v1.x * r.v1.x); sum += (double)(r.v1.y * r.v1.y); sum += (double)(r.v1.z * r.v1.z); sum += (double)(r.v1.w * r.v1.w);
+    sum += (double)(r.t * r.t);
+    sum = wave_sum_d(sum);                                      // the same total in every lane
+    if (!nm_l2_order_safe(sum, n)) sum = rms_serial_sumsq<false>(x, nullptr, n);      // wave-uniform; x still holds the row (this wave alone stores to it, later)
+    return nm_l2_scale(sum, eps);
+}
+
+// ---- GROUP_NORM: the workgroup's side of norm_order.h.  A 1024-thread workgroup per (group, i03).  The group is `rows` = ne1 * step rows of ne0 floats, row r at
+// nm_gn_row(x, r, ...) (rows, channels and batches may be strided, so alignment is decided per row); a row is nq = ne0 / 4 float4 ITEMS and ne0 % 4 items of one
+// element; thread t owns the items t, t + 1024, ... of the rows laid end to end.
+struct gn_group {
+    const char * x; char * y;                                   // the group's first row in the source and in the destination
+    int64_t ne0, ne1, rows, nb1, nb2, dnb1, dnb2;
+    int64_t nq, ipr, items, N;                                  // float4 items per row, items per row, items of the group, elements of the group
+};
+struct gn_item { f32x4 v; int cnt; int64_t row; int col; };     // cnt = 4: v holds elements col .. col + 3 of the row; cnt = 1: v.x holds element col
+__device__ __forceinline__ gn_item gn_load(const gn_group & G, int64_t item) {
+    gn_item it;
+    it.row = item / G.ipr;
+    const int64_t j = item - it.row * G.ipr;
+    const float * xr = nm_gn_row(G.x, it.row, G.ne1, G.nb1, G.nb2);
+    if (j < G.nq) { it.cnt = 4; it.col = (int)(4 * j); it.v = rms_load4(xr, j, (((uintptr_t) xr) & 15) == 0); }
+    else          { it.cnt = 1; it.col = (int)(4 * G.nq + (j - G.nq)); it.v = f32x4{ xr[it.col], 0, 0, 0 }; }
+    return it;
+}
+// S = sum x with A = sum |x| through the same tree.  `first` = the thread's item tid, loaded by the caller (ignored when tid >= items).  Contains a barrier.
+__device__ __forceinline__ void gn_block_sum_1024(const gn_group & G, const gn_item & first, double * part_s, double * part_a, double & S, double & A) {
+    const int tid = threadIdx.x;
+    double s = 0.0, a = 0.0;
+    gn_item it = first;
+    for (int64_t i = tid; i < G.items; i += 1024) {
+        if (i != tid) it = gn_load(G, i);
+        s += (double) it.v.x; a += (double) fabsf(it.v.x);
+        if (it.cnt == 4) { s += (double) it.v.y; s += (double) it.v.z; s += (double) it.v.w; a += (double) fabsf(it.v.y); a += (double) fabsf(it.v.z); a += (double) fabsf(it.v.w); }
+    }
+    s = wave_sum_d(s); a = wave_sum_d(a);
+    if ((tid & 63) == 0) { part_s[tid >> 6] = s; part_a[tid >> 6] = a; }
+    __syncthreads();
+    S = part_s[0]; A = part_a[0];
+#pragma unroll
+    for (int w = 1; w < 16; w++) { S += part_s[w]; A += part_a[w]; }
+}
+// V = sum of the float squares of the centred values, as a tree of doubles.  Contains a barrier.
+__device__ __forceinline__ double gn_block_var_sum_1024(const gn_group & G, const gn_item & first, float mean, double * part) {
+    const int tid = threadIdx.x;
+    double p = 0.0;
+    gn_item it = first;
+    for (int64_t i = tid; i < G.items; i += 1024) {
+        if (i != tid) it = gn_load(G, i);
+        { const float v = it.v.x - mean; p += (double)(v * v); }
+        if (it.cnt == 4) {
+            const float vy = it.v.y - mean, vz = it.v.z - mean, vw = it.v.w - mean;
+            p += (double)(vy * vy); p += (double)(vz * vz); p += (double)(vw * vw);
+        }
+    }
+    p = wave_sum_d(p);
+    if ((tid & 63) == 0) part[tid >> 6] = p;
+    __syncthreads();
+    double V = part[0];
+#pragma unroll
+    for (int w = 1; w < 16; w++) V += part[w];
+    return V;
+}
+// the two-level serial chains of norm_order.h (nm_gn_serial_sum, nm_gn_serial_var_sum) by wave 0, each row's chain batched 64 terms at a time as norm_serial_sum is
+static __device__ __noinline__ double gn_serial_row_sq(const float * x, int64_t n, float mean) {
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    float cur = lane < n ? x[lane] : 0.0f;
+    for (int64_t i = 0; i < n; i += 64) {
+        const float nxt = i + 64 + lane < n ? x[i + 64 + lane] : 0.0f;      // the next batch is requested before this one is added
+        const float v = cur - mean;
+        s = norm_chain(s, v * v, n - i >= 64 ? 64 : (int)(n - i));
+        cur = nxt;
+    }
+    return s;
+}
+// (the loops over the rows are inlined: a called function that calls another needs a stack frame, and the kernel would need scratch memory)
+__device__ __forceinline__ double gn_serial_sum(const char * x, int64_t ne0, int64_t ne1, int64_t rows, int64_t nb1, int64_t nb2) {
+    double S = 0.0;
+    for (int64_t row = 0; row < rows; row++) S += norm_serial_sum(nm_gn_row(x, row, ne1, nb1, nb2), ne0);
+    return S;
+}
+__device__ __forceinline__ double gn_serial_var_sum(const char * x, int64_t ne0, int64_t ne1, int64_t rows, int64_t nb1, int64_t nb2, float mean) {
+    double V = 0.0;
+    for (int64_t row = 0; row < rows; row++) V += gn_serial_row_sq(nm_gn_row(x, row, ne1, nb1, nb2), ne0, mean);
+    return V;
+}
+// mean and variance from the tree totals, as norm_mean and norm_variance: uniform branches, one LDS double each, a barrier behind each serial pass.  x must still hold the
+// group: no thread of an in-place launch stores before BOTH have returned.
+__device__ __forceinline__ float gn_mean(double S, double A, const gn_group & G, double * slot) {
+    if (!nm_gn_sum_order_safe(S, A, G.N)) {
+        if (threadIdx.x < 64) { const double s = gn_serial_sum(G.x, G.ne0, G.ne1, G.rows, G.nb1, G.nb2); if (threadIdx.x == 0) *slot = s; }
+        __syncthreads();
+        S = *slot;
+    }
+    return nm_gn_mean(S, G.N);
+}
+__device__ __forceinline__ float gn_variance(double V, float mean, const gn_group & G, double * slot) {
+    if (!nm_gn_var_order_safe(V, G.N)) {
+        if (threadIdx.x < 64) { const double s = gn_serial_var_sum(G.x, G.ne0, G.ne1, G.rows, G.nb1, G.nb2, mean); if (threadIdx.x == 0) *slot = s; }
+        __syncthreads();
+        V = *slot;
+    }
+    return nm_gn_variance(V, G.N);
+}
+
 // workgroup barrier for data exchanged through LDS only: __syncthreads() also drains vmcnt, i.e. waits for every global load in flight --
 // which is exactly what a latency-bound kernel prefetches ACROSS its phases.  LDS operations of a wave complete in order: lgkmcnt(0) + s_barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -75,3 +75,83 @@ NM_FN int nm_var_order_safe(double V, int64_t n) {
     const double r = (double)(2 * nm_var_terms(n) + 16) * 0x1p-53;
     return nm_variance(V * (1.0 - r), n) == nm_variance(V * (1.0 + r), n);
 }
+
+// ======== L2_NORM and GROUP_NORM: the other two normalisation nodes, under the same contract (k_l2_norm, k_l2_norm_wave, k_group_norm of ops.hip; tests/l2_group_norm_host.c,
+// which tests/test_l2_group_norm_model.py compiles alone with gcc and compares with the reference's CPU backend) ========
+//
+// ggml_compute_forward_l2_norm_f32 (ggml-cpu/ops.cpp:4051-4092), per row of n floats:
+//   sum      = sum of (double)(x[i] * x[i]), serially, i ascending, from +0.0                a float product, then widened (ops.cpp:4077-4080)
+//   scale    = 1.0f / fmaxf(sqrtf((float) sum), eps)                                          ops.cpp:4086 (sqrtf takes a float: the double is converted first)
+//   y[i]     = x[i] * scale                                                                   ggml_vec_scale_f32: one float multiply
+// fmaxf returns its non-NaN operand: a row that holds a NaN has scale = 1 / eps (inf with eps = 0), so only the NaN elements and any 0 * inf are NaN; a row that holds an
+// inf has scale = 0; a row of zeros has scale = 1 / eps.
+//
+// ggml_compute_forward_group_norm_f32 (ops.cpp:3956-4029), per (group, i03); the group's rows are (i02 in [start, end), i01 in [0, ne01)), N = ne00 * ne01 * (end - start):
+//   S        = sum over the rows, (i02, i01) ascending, of sumr;  sumr = sum of (double) x[i00], serially from 0.0 per row      ops.cpp:3988-3999
+//   mean     = (float)(S / (double) N)                                                        ops.cpp:4000: a double division, then the conversion (NORM divides floats)
+//   v        = x - mean
+//   V        = sum over the rows of sumr2;  sumr2 = sum of (double)(v * v), serially from 0.0 per row                          ops.cpp:4002-4017: a scalar loop, no groups of 8
+//   variance = (float)(V / (double) N)                                                        ops.cpp:4018
+//   scale    = 1.0f / sqrtf(variance + eps)                                                   ops.cpp:4019 (nm_scale)
+//   y        = v * scale                                                                      two roundings, never an fma (nm_out)
+NM_FN int nm_same_float(float a, float b) {                 // equal AND the same zero: -0 == +0 compares equal, but a mean of -0 and one of +0 give a -0 element different signs
+    uint32_t p, q; __builtin_memcpy(&p, &a, 4); __builtin_memcpy(&q, &b, 4);
+    return a == b && p == q;
+}
+
+// ---- the float steps ----
+NM_FN float nm_l2_scale(double sum, float eps)      { return 1.0f / fmaxf(sqrtf((float) sum), eps); }
+NM_FN float nm_l2_out(float x, float scale)         { return x * scale; }
+NM_FN float nm_gn_mean(double S, int64_t N)         { return (float)((S + 0.0) / (double) N); }     // (S + 0.0: as in nm_mean, the chains start from +0.0 and never total -0)
+NM_FN float nm_gn_variance(double V, int64_t N)     { return (float)(V / (double) N); }
+NM_FN int64_t nm_gn_channels_per_group(int64_t C, int64_t n_groups) { return (C + n_groups - 1) / n_groups; }
+
+// ---- the serial chains: the reference's own order.  GROUP_NORM's has two levels: a chain from 0.0 per row, the rows' totals added in (i02, i01) order.  `x` is the group's
+// first row (channel `start` of batch i03); nb1, nb2 in bytes, as the tensor has them. ----
+NM_FN double nm_l2_serial_sumsq(const float * x, int64_t n) {
+    double sum = 0.0;
+    for (int64_t i = 0; i < n; i++) sum += (double)(x[i] * x[i]);
+    return sum;
+}
+NM_FN double nm_gn_serial_row_sq(const float * x, int64_t n, float mean) {
+    double s = 0.0;
+    for (int64_t i = 0; i < n; i++) { const float v = x[i] - mean; s += (double)(v * v); }
+    return s;
+}
+NM_FN const float * nm_gn_row(const char * x, int64_t row, int64_t ne1, int64_t nb1, int64_t nb2) {      // row = (i02 - start) * ne1 + i01
+    return (const float *)(x + (row % ne1) * nb1 + (row / ne1) * nb2);
+}
+NM_FN double nm_gn_serial_sum(const char * x, int64_t ne0, int64_t ne1, int64_t step, int64_t nb1, int64_t nb2) {
+    double S = 0.0;
+    for (int64_t row = 0; row < ne1 * step; row++) S += nm_serial_sum(nm_gn_row(x, row, ne1, nb1, nb2), ne0);
+    return S;
+}
+NM_FN double nm_gn_serial_var_sum(const char * x, int64_t ne0, int64_t ne1, int64_t step, int64_t nb1, int64_t nb2, float mean) {
+    double V = 0.0;
+    for (int64_t row = 0; row < ne1 * step; row++) V += nm_gn_serial_row_sq(nm_gn_row(x, row, ne1, nb1, nb2), ne0, mean);
+    return V;
+}
+
+// ---- ORDER: the three interval tests of these two nodes.  The reference's nested order (a chain per row, then a chain over the rows' totals; its additions to 0.0 are exact)
+// is ONE particular summation tree of the N terms, and so is whatever a wave or a workgroup does instead.  The bound the tests rest on (Higham 4.2, as above: any double sum
+// of m terms lies within gamma_(m-1) * sum|t_i| of the exact sum) holds for EVERY such tree, so two of them differ by at most 2 gamma_(m-1) * sum|t_i|.
+//
+// L2's sum: n non-negative terms, each an exact float product that every order shares -- RMS_NORM's structure.  All the op sees is (float) sum, monotonic.  The ends are
+// formed by multiplication: sum = inf (a square overflowed, or an inf in the row: every order shares it) gives inf == inf, safe; sum = NaN compares unequal and the serial
+// chain gives NaN again.
+NM_FN int nm_l2_order_safe(double sum, int64_t n) {
+    const double r = (double)(2 * n + 16) * 0x1p-53;
+    return (float)(sum * (1.0 - r)) == (float)(sum * (1.0 + r));
+}
+// GROUP_NORM's S: N signed terms, so A = sum|x| through the same tree is needed, as for nm_sum_order_safe, and the comparison is of what THIS op sees, (float)(S / N):
+// division by a positive N and the conversion are monotonic.  The two ends must also be the same zero (nm_same_float): a serial S of -1e-60 and a tree's +1e-60 both give a
+// mean that compares equal to 0, with different signs.  NaN / inf: as nm_sum_order_safe.
+NM_FN int nm_gn_sum_order_safe(double S, double A, int64_t N) {
+    const double d = A * ((double)(2 * N + 16) * 0x1p-53);
+    return nm_same_float(nm_gn_mean(S - d, N), nm_gn_mean(S + d, N));
+}
+// GROUP_NORM's V: N non-negative terms (one float square per element: N of them, not nm_var_terms), on (float)(V / N).  inf and NaN: as nm_var_order_safe.
+NM_FN int nm_gn_var_order_safe(double V, int64_t N) {
+    const double r = (double)(2 * N + 16) * 0x1p-53;
+    return nm_gn_variance(V * (1.0 - r), N) == nm_gn_variance(V * (1.0 + r), N);
+}

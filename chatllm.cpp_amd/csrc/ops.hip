@@ -102,6 +102,130 @@ extern "C" int cllm_op_norm(void * stream, const cllm_tensor * src, cllm_tensor 
 }
 
 // ================================================================================================
+// L2_NORM     ggml_compute_forward_l2_norm_f32, ggml-cpu/ops.cpp:4051-4092 (ggml::norm_p2: the query and key of a gated delta net's linear attention, per head)
+//   sum of x*x in double, scale = 1/fmaxf(sqrtf((float) sum), eps), y = x*scale.  The arithmetic and its order: norm_order.h; the trees and fallbacks: common.h.
+// Two launch shapes.  Rows longer than L2_WAVE_ROW_MAX: k_rms_norm's shape, one 1024-thread workgroup per row.  Shorter rows (128 per head, heads x tokens of them): one
+// wave per row, four rows per 256-thread workgroup, the row in registers between the sum and the store, no barrier and no LDS anywhere (the interval test's outcome
+// differs from wave to wave).  dst may be src in both: a row is stored by those who summed it, behind the last barrier (workgroup) or by the same wave (wave per row).
+// ================================================================================================
+static constexpr int64_t L2_WAVE_ROW_MAX = 512;       // the longest row the wave-per-row shape takes (8 elements per lane and a leftover): DESIGN.md has the measurement
+static constexpr int     L2_WAVE_ROWS    = 4;         // rows (waves) per workgroup of that shape
+
+__global__ void __launch_bounds__(1024) k_l2_norm(tview s, tview d, float eps) {
+    const int64_t row = blockIdx.x;
+    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
+    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
+    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const int64_t n = s.ne[0], nq = n >> 2;
+    const int tid = threadIdx.x;
+    __shared__ double part[16];
+    const bool aligned = (((uintptr_t) x) & 15) == 0, y_aligned = (((uintptr_t) y) & 15) == 0;
+    const f32x4 first = tid < nq ? rms_load4(x, tid, aligned) : f32x4{0, 0, 0, 0};
+    const double sum = rms_block_sumsq_1024(x, n, first, part);
+    const float scale = l2_block_scale(sum, n, eps, x, part);
+    f32x4 v = first;
+    for (int64_t q = tid; q < nq; q += 1024) {
+        if (q != tid) v = rms_load4(x, q, aligned);
+        const f32x4 o = { nm_l2_out(v.x, scale), nm_l2_out(v.y, scale), nm_l2_out(v.z, scale), nm_l2_out(v.w, scale) };
+        float * yq = y + 4 * q;
+        if (y_aligned) *(f32x4 *) yq = o;
+        else { yq[0] = o.x; yq[1] = o.y; yq[2] = o.z; yq[3] = o.w; }
+    }
+    if (4 * nq + tid < n) y[4 * nq + tid] = nm_l2_out(x[4 * nq + tid], scale);
+}
+
+__global__ void __launch_bounds__(64 * L2_WAVE_ROWS) k_l2_norm_wave(tview s, tview d, int64_t rows, float eps) {
+    const int64_t row = (int64_t) blockIdx.x * L2_WAVE_ROWS + (threadIdx.x >> 6);
+    if (row >= rows) return;                                    // a wave past the last row: nothing below waits for it
+    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
+    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
+    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const int64_t n = s.ne[0];
+    const int lane = threadIdx.x & 63, nq = (int)(n >> 2);
+    const bool y_aligned = (((uintptr_t) y) & 15) == 0;
+    const l2_wave_row r = l2_wave_load(x, n, (((uintptr_t) x) & 15) == 0);
+    const float scale = l2_wave_scale(r, n, eps, x);
+    auto store4 = [&](int q, f32x4 v) {
+        const f32x4 o = { nm_l2_out(v.x, scale), nm_l2_out(v.y, scale), nm_l2_out(v.z, scale), nm_l2_out(v.w, scale) };
+        float * yq = y + 4 * q;
+        if (y_aligned) *(f32x4 *) yq = o;
+        else { yq[0] = o.x; yq[1] = o.y; yq[2] = o.z; yq[3] = o.w; }
+    };
+    if (lane < nq)      store4(lane, r.v0);
+    if (lane + 64 < nq) store4(lane + 64, r.v1);
+    if (4 * nq + lane < n) y[4 * nq + lane] = nm_l2_out(r.t, scale);
+}
+
+extern "C" int cllm_op_l2_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "l2_norm: null");
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "l2_norm: type (F32 only)");
+    if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "l2_norm: shape");
+    if (src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "l2_norm: rows must be dense");
+    if (!(eps >= 0.0f)) FAIL(CLLM_E_INVALID, "l2_norm: eps must be >= 0");          // (NaN included) the reference asserts eps >= 0, ops.cpp:4069
+    const int64_t rows = t_nrows(src);
+    if (rows == 0 || src->ne[0] == 0) return CLLM_OK;
+    if (rows > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "l2_norm: more than 2^31 - 1 rows");
+    if (src->ne[0] <= L2_WAVE_ROW_MAX)
+        hipLaunchKernelGGL(k_l2_norm_wave, dim3((unsigned)((rows + L2_WAVE_ROWS - 1) / L2_WAVE_ROWS)), dim3(64 * L2_WAVE_ROWS), 0, (hipStream_t) stream, tv(src), tv(dst), rows, eps);
+    else
+        hipLaunchKernelGGL(k_l2_norm, dim3((unsigned) rows), dim3(1024), 0, (hipStream_t) stream, tv(src), tv(dst), eps);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// ================================================================================================
+// GROUP_NORM  ggml_compute_forward_group_norm_f32, ggml-cpu/ops.cpp:3956-4029 (GroupNorm::forward before its affine: MUL and ADD by a [1, 1, C] view stay nodes of their own)
+//   per (group, i03), over the group's ne01 * step rows: S in double, a chain per row and a chain over the rows; mean = (float)(S / N); the centred squares in float,
+//   V in double the same way; variance = (float)(V / N); scale = 1/sqrtf(variance+eps), y = (x - mean) * scale.  The arithmetic and its order: norm_order.h; the
+//   workgroup's trees and fallbacks: common.h.
+// one workgroup per (group, i03), three passes over the group (S with A, V, the stores; a thread's first item stays in registers, which is the whole group where it has at
+// most 1024 items); float4 traffic where a row's start is 16-byte aligned, decided per row on either side.  dst may be src (group_norm_inplace is what the host uses):
+// every store comes after the last barrier of gn_variance, behind every read of both sums and of both fallbacks.
+// ================================================================================================
+__global__ void __launch_bounds__(1024) k_group_norm(tview s, tview d, int64_t cpg, int64_t groups, float eps) {
+    const int64_t g = blockIdx.x % groups, i3 = blockIdx.x / groups;
+    const int64_t start = g * cpg, end = start + cpg < s.ne[2] ? start + cpg : s.ne[2], step = end - start;
+    if (step <= 0) return;                                      // an empty group (C = 5 in 4 groups: the last one) touches nothing; the launcher starts none
+    gn_group G;
+    G.x = s.data + start * s.nb[2] + i3 * s.nb[3]; G.y = d.data + start * d.nb[2] + i3 * d.nb[3];
+    G.ne0 = s.ne[0]; G.ne1 = s.ne[1]; G.rows = s.ne[1] * step; G.nb1 = s.nb[1]; G.nb2 = s.nb[2]; G.dnb1 = d.nb[1]; G.dnb2 = d.nb[2];
+    G.nq = G.ne0 >> 2; G.ipr = G.nq + (G.ne0 & 3); G.items = G.rows * G.ipr; G.N = G.ne0 * G.rows;
+    const int tid = threadIdx.x;
+    __shared__ double part[3][16];
+    __shared__ double slot[2];
+    const gn_item first = tid < G.items ? gn_load(G, tid) : gn_item{ f32x4{0, 0, 0, 0}, 1, 0, 0 };
+    double S, A;
+    gn_block_sum_1024(G, first, part[0], part[1], S, A);
+    const float mean = gn_mean(S, A, G, &slot[0]);
+    const double V = gn_block_var_sum_1024(G, first, mean, part[2]);
+    const float scale = nm_scale(gn_variance(V, mean, G, &slot[1]), eps);
+    gn_item it = first;
+    for (int64_t i = tid; i < G.items; i += 1024) {
+        if (i != tid) it = gn_load(G, i);
+        float * yr = (float *)(G.y + (it.row % G.ne1) * G.dnb1 + (it.row / G.ne1) * G.dnb2) + it.col;
+        if (it.cnt == 4) {
+            const f32x4 o = { nm_out(it.v.x, mean, scale), nm_out(it.v.y, mean, scale), nm_out(it.v.z, mean, scale), nm_out(it.v.w, mean, scale) };
+            if ((((uintptr_t) yr) & 15) == 0) *(f32x4 *) yr = o;
+            else { yr[0] = o.x; yr[1] = o.y; yr[2] = o.z; yr[3] = o.w; }
+        } else yr[0] = nm_out(it.v.x, mean, scale);
+    }
+}
+
+extern "C" int cllm_op_group_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, int n_groups, float eps) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "group_norm: null");
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "group_norm: type (F32 only)");
+    if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "group_norm: shape");
+    if (src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "group_norm: rows must be dense");
+    if (n_groups <= 0) FAIL(CLLM_E_INVALID, "group_norm: n_groups must be > 0");
+    if (src->ne[2] > 0x7fffffff || src->ne[3] > 0x7fffffff || src->ne[2] * src->ne[3] > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "group_norm: more than 2^31 - 1 (channel, batch) pairs");
+    if (t_nrows(src) == 0 || src->ne[0] == 0) return CLLM_OK;
+    const int64_t C = src->ne[2], cpg = nm_gn_channels_per_group(C, n_groups), groups = (C + cpg - 1) / cpg;      // (the groups that hold a channel: the others are empty)
+    hipLaunchKernelGGL(k_group_norm, dim3((unsigned)(groups * src->ne[3])), dim3(1024), 0, (hipStream_t) stream, tv(src), tv(dst), cpg, groups, eps);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// ================================================================================================
 // ROPE        ggml_compute_forward_rope_flt<float>, ggml-cpu/ops.cpp:5589-5865
 //   theta_i built by ITERATED fp32 multiplication (rope_theta, common.h), cos/sin per (token, pair),
 //   YaRN mixing (rope_yarn :5596-5611).  One workgroup per token: the first n_dims/2 threads build

@@ -396,6 +396,12 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
             float eps; memcpy(&eps, op->op_params, 4);
             return f32_dense(a) && op->type == GGML_TYPE_F32 && op->nb[0] == 4 && eps >= 0.0f;
         }
+        case GGML_OP_L2_NORM: {    // cllm_op_l2_norm's own predicates: dense F32 rows on both sides, eps >= 0 (not NaN)
+            float eps; memcpy(&eps, op->op_params, 4);
+            return f32_dense(a) && f32_dense(op) && eps >= 0.0f;
+        }
+        case GGML_OP_GROUP_NORM:   // cllm_op_group_norm's: dense F32 rows on both sides, n_groups > 0 (eps as it is); MUL and ADD of a GroupNorm's affine stay their own nodes
+            return f32_dense(a) && f32_dense(op) && op->op_params[0] > 0 && a->ne[2] * a->ne[3] <= 0x7fffffff;
         case GGML_OP_ADD: case GGML_OP_MUL: case GGML_OP_DIV: return a->type == GGML_TYPE_F32 && b->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && ggml_can_repeat(b, a);
         case GGML_OP_SUM_ROWS: return f32_dense(a) && f32_dense(op);
         case GGML_OP_TOP_K: return f32_dense(a) && op->type == GGML_TYPE_I32 && a->ne[0] <= 4096;
@@ -983,6 +989,8 @@ ggml_status walk(walk_ctx & w, fuse_plan & plan, sig_writer * sw) {
             case GGML_OP_MUL_MAT_ID:     rc = issue_mat_mul_id(w, io); break;
             case GGML_OP_RMS_NORM:       { float eps; memcpy(&eps, n->op_params, 4); rc = E(cllm_op_rms_norm, st, &da, &d, eps); } break;
             case GGML_OP_NORM:           { float eps; memcpy(&eps, n->op_params, 4); rc = E(cllm_op_norm, st, &da, &d, eps); } break;
+            case GGML_OP_L2_NORM:        { float eps; memcpy(&eps, n->op_params, 4); rc = E(cllm_op_l2_norm, st, &da, &d, eps); } break;
+            case GGML_OP_GROUP_NORM:     { float eps; memcpy(&eps, n->op_params + 1, 4); rc = E(cllm_op_group_norm, st, &da, &d, (int) n->op_params[0], eps); } break;
             case GGML_OP_ADD:            rc = alt == ALT_MOE_COMBINE ? issue_moe_combine(w, plan, i, io) : E(cllm_op_add, st, &da, &db, &d); break;
             case GGML_OP_MUL:            rc = issue_mul(w, plan, i, io); break;
             case GGML_OP_DIV:            rc = E(cllm_op_div, st, &da, &db, &d); break;

@@ -108,6 +108,8 @@ SIGNATURES = {
     "cllm_op_rms_norm": (C.c_int, [_P, _T, _T, C.c_float]),
     "cllm_op_rms_norm_mul": (C.c_int, [_P, _T, _T, _T, C.c_float]),
     "cllm_op_norm": (C.c_int, [_P, _T, _T, C.c_float]),
+    "cllm_op_l2_norm": (C.c_int, [_P, _T, _T, C.c_float]),
+    "cllm_op_group_norm": (C.c_int, [_P, _T, _T, C.c_int, C.c_float]),
     "cllm_op_rope": (C.c_int, [_P, _T, _T, _T, _T, C.POINTER(RopeParams)]),
     "cllm_op_soft_max": (C.c_int, [_P, _T, _T, _T, C.c_float, C.c_float]),
     "cllm_op_diag_mask_inf": (C.c_int, [_P, _T, _T, C.c_int]),

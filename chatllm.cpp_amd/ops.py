@@ -82,6 +82,20 @@ def norm(a, eps, dst=None):
     return dst
 
 
+def l2_norm(a, eps, dst=None):
+    """ggml::norm_p2 (src/layers.cpp:863; dst is a: ggml_l2_norm_inplace): every row divided by max(its Euclidean length, eps)"""
+    dst = dst or Tensor(F32, a.ne)
+    _l.check(_l.get().cllm_op_l2_norm(None, _ref(a), _ref(dst), eps), "l2_norm")
+    return dst
+
+
+def group_norm(a, n_groups, eps, dst=None):
+    """ggml::group_norm / group_norm_inplace (dst is a): GroupNorm before its affine, which stays mul and add by a [1, 1, C] view"""
+    dst = dst or Tensor(F32, a.ne)
+    _l.check(_l.get().cllm_op_group_norm(None, _ref(a), _ref(dst), n_groups, eps), "group_norm")
+    return dst
+
+
 def rope_ext(a, pos, freq_factors, n_dims, mode, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0,
              attn_factor=1.0, beta_fast=0.0, beta_slow=0.0, inplace=False):
     """ggml::rope_ext / rope_ext_inplace"""

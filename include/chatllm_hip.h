@@ -221,6 +221,20 @@ CLLM_API int cllm_op_rms_norm_mul(void * stream, const cllm_tensor * src, const 
  * a NaN or an inf is NaN in every element, as there; NaN payloads are not part of the contract).  CLLM_E_UNSUPPORTED: another type, rows that are not dense;
  * CLLM_E_INVALID: null, shapes that differ, eps < 0 or NaN (the reference asserts eps >= 0).  An empty tensor: CLLM_OK, no launch.  A declined call leaves dst untouched. */
 CLLM_API int cllm_op_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps);
+/* GGML_OP_L2_NORM       ggml_compute_forward_l2_norm_f32  (ggml-cpu/ops.cpp:4051-4092): ggml::norm_p2 (src/layers.cpp:863), the query and key of a gated delta net's
+ * linear attention.  y = x / fmaxf(sqrtf(sum x^2), eps) per row, the sum in double in index order.  F32 -> F32, rows of any ne[0] >= 1 with nb[0] == 4 (nb[1..3]
+ * free), dst may be src; every word has the bits of the reference's CPU build.  As there, fmaxf drops a NaN: a row holding a NaN is scaled by 1 / eps (only its NaN
+ * elements and any 0 * inf are NaN), a row holding an inf by 0, a row of zeros by 1 / eps.  CLLM_E_UNSUPPORTED: another type, rows that are not dense; CLLM_E_INVALID:
+ * null, shapes that differ, eps < 0 or NaN (the reference asserts eps >= 0).  An empty tensor: CLLM_OK, no launch.  A declined call leaves dst untouched. */
+CLLM_API int cllm_op_l2_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps);
+/* GGML_OP_GROUP_NORM    ggml_compute_forward_group_norm_f32  (ggml-cpu/ops.cpp:3956-4029): GroupNorm::forward before its affine (src/layers.cpp:2153-2207; MUL and ADD by a
+ * [1, 1, C] view stay nodes of their own).  Over ne = [ne0, ne1, C, ne3]: group g of n_groups covers the channels [g * cpg, min((g + 1) * cpg, C)), cpg = ceil(C /
+ * n_groups); a group without channels touches nothing.  Per (group, ne3 index): mean and variance over the group's elements, the sums in double in the reference's order
+ * (a chain per row, the rows in channel-major order), y = (x - mean) * (1 / sqrtf(variance + eps)).  F32 -> F32, nb[0] == 4 (rows, channels and batches may be strided),
+ * dst may be src (group_norm_inplace); every word has the bits of the reference's CPU build; eps is used as it is, as there.  CLLM_E_UNSUPPORTED: another type, rows that
+ * are not dense, ne[2] * ne[3] beyond 2^31 - 1; CLLM_E_INVALID: null, shapes that differ, n_groups <= 0.  An empty tensor: CLLM_OK, no launch.  A declined call leaves
+ * dst untouched. */
+CLLM_API int cllm_op_group_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, int n_groups, float eps);
 
 typedef struct cllm_rope_params {      /* op_params of GGML_OP_ROPE (ggml.c ggml_rope_impl) */
     int32_t n_dims, mode, n_ctx_orig;  /* mode 0 = NORMAL (i,i+1), 2 = NEOX (i, i+n_dims/2) */
