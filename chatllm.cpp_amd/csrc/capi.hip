@@ -304,6 +304,10 @@ static int check_mm(const cllm_tensor * src0, const cllm_tensor * src1, const cl
     if (src0->nb[0] != cllm_type_size(src0->type) || src1->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "%s: rows must be dense", name);
     if (src0->ne[0] % cllm_blck_size(src0->type)) FAIL(CLLM_E_INVALID, "%s: K not a multiple of the block size", name);
     if (src0->type == CLLM_TYPE_Q4_1 && !rows_aligned(src0)) FAIL(CLLM_E_UNSUPPORTED, "%s: Q4_1 rows must be %d-byte aligned", name, wtype_row_align(src0->type));
+    // dst rows and planes are whole floats apart in every kernel; the float kernels load src0 / src1 element by element (the quantized ones: mm_wdata_and_alignment, kq_check)
+    if (((uintptr_t) dst->data | dst->nb[1] | dst->nb[2] | dst->nb[3]) % 4) FAIL(CLLM_E_INVALID, "%s: dst stride", name);
+    if (!is_quant(src0->type) && (!rows_aligned(src0) || ((uintptr_t) src1->data | src1->nb[1] | src1->nb[2] | src1->nb[3]) % 4))
+        FAIL(CLLM_E_UNSUPPORTED, "%s: float operands must be aligned to their elements", name);
     return CLLM_OK;
 }
 

@@ -137,7 +137,10 @@ static int launch_T(hipStream_t st, const tview & w, const tview & x, const tvie
     const int64_t K = w.ne[0];
     if (w.ne[2] * w.ne[3] > 65535) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_f: too many batches");
     // llamafile_sgemm takes the product when n >= 2, k % 8 == 0, m % 4 == 0 (sgemm.cpp:3691, 488, 503-517); else the vec_dot loop
-    const bool t8 = x.ne[1] >= 2 && K % 8 == 0 && w.ne[1] % 4 == 0;
+    // an F32 src0 reads src1 in place, and tinyBLAS is tried only on a contiguous src1 (ggml-cpu.c:1269-1271); an F16 src0 reads its dense fp16 copy of any src1
+    bool x_cont = true;
+    for (int64_t i = 1, next = 4 * K; i < 4; next *= x.ne[i], i++) if (x.ne[i] != 1 && x.nb[i] != next) x_cont = false;
+    const bool t8 = x.ne[1] >= 2 && K % 8 == 0 && w.ne[1] % 4 == 0 && (sizeof(T) == 2 || x_cont);
     if (t8) hipLaunchKernelGGL((k_mul_mat_f_t8<T>), dim3((unsigned)((w.ne[1] + 31) / 32), (unsigned)(w.ne[2] * w.ne[3])), dim3(256), 0, st, w, x, d);
     else    hipLaunchKernelGGL((k_mul_mat_f_vd<T>), dim3((unsigned)((w.ne[1] + 15) / 16), (unsigned)(w.ne[2] * w.ne[3])), dim3(256), 0, st, w, x, d);
     LAUNCH_CHECK();

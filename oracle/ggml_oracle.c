@@ -1341,12 +1341,15 @@ int orc_mul_mat(const orc_tensor * src0, const orc_tensor * src1, orc_tensor * d
     const size_t rs = orc_row_size(vt, K);
     void * arow = malloc(rs);
     const int64_t r2 = src1->ne[2] / src0->ne[2], r3 = src1->ne[3] / src0->ne[3];
+    /* an F32 src0 reads src1 in place: tinyBLAS takes it only when src1 is contiguous (ggml-cpu.c:1269-1271, ggml_is_contiguous; an F16 src0 reads the dense fp16 copy) */
+    int src1_cont = 1;
+    for (size_t i = 1, next = 4 * (size_t) K; i < 4; next *= (size_t) src1->ne[i], i++) if (src1->ne[i] != 1 && src1->nb[i] != next) src1_cont = 0;
     for (int64_t i13 = 0; i13 < src1->ne[3]; i13++)
     for (int64_t i12 = 0; i12 < src1->ne[2]; i12++)
     for (int64_t i11 = 0; i11 < src1->ne[1]; i11++) {
         convert_row(vt, (const float *) tptr(src1, 0, i11, i12, i13), arow, K);
         /* llamafile_sgemm takes F16 / F32 src0 for n >= 2, k % 8 == 0, m % 4 == 0 (sgemm.cpp:3691, 488, 503-517) */
-        const int tiny = g_order == ORC_ORDER_AVX2 && (src0->type == ORC_F16 || src0->type == ORC_F32) && src1->ne[1] >= 2 && K % 8 == 0 && src0->ne[1] % 4 == 0;
+        const int tiny = g_order == ORC_ORDER_AVX2 && (src0->type == ORC_F16 || (src0->type == ORC_F32 && src1_cont)) && src1->ne[1] >= 2 && K % 8 == 0 && src0->ne[1] % 4 == 0;
         for (int64_t i01 = 0; i01 < src0->ne[1]; i01++) {
             const void * w = tptr(src0, 0, i01, i12 / r2, i13 / r3);
             float v;

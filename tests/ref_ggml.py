@@ -2,7 +2,8 @@
 through its public ggml C API with ctypes: ggml_init, ggml_new_tensor_4d, the op constructor, ggml_build_forward_expand,
 ggml_graph_compute_with_ctx.  The oracle of the element-wise ops that oracle/ref_ops.c does not expose (TANH, RELU, SIGMOID, GELU,
 GELU_QUICK, SQR), of SCALE with a bias, broadcast ADD / MUL / DIV, DIAG_MASK_INF and of ROPE over a view (ggml_view_4d), out of place and
-in place; of SET_ROWS, CPY / CONT, GET_ROWS between views (ggml_view_4d, ggml_permute, ggml_transpose) and of SOFT_MAX with a mask tensor.
+in place; of SET_ROWS, CPY / CONT, GET_ROWS between views (ggml_view_4d, ggml_permute, ggml_transpose), of SOFT_MAX with a mask tensor and of
+MUL_MAT between views of a weight buffer and of a src1 buffer.
 Also: the input sets the CPU and the GPU tests of the unary ops share."""
 import ctypes as C
 import os
@@ -65,7 +66,7 @@ def libs():
         base.ggml_new_tensor_1d.restype, base.ggml_new_tensor_1d.argtypes = P, [P, C.c_int, C.c_int64]
         for name in ("ggml_set_rows",):
             getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P, P]
-        for name in ("ggml_cpy", "ggml_get_rows"):
+        for name in ("ggml_cpy", "ggml_get_rows", "ggml_mul_mat"):
             getattr(base, name).restype, getattr(base, name).argtypes = P, [P, P, P]
         base.ggml_cont.restype, base.ggml_cont.argtypes = P, [P, P]
         for name in ("ggml_soft_max_ext", "ggml_soft_max_ext_inplace"):
@@ -316,6 +317,26 @@ def get_rows(table, type_, ne, idx0, idx_view):
         out = base.ggml_get_rows(ctx, t, _view(base, ctx, _parent(base, ctx, GGML_TYPE_I32, _bytes(idx0)), idx_view))
         return out, [(out, shape, np.float32)]
     return _graph(table.nbytes + idx0.nbytes + 4 * int(np.prod(shape)) + (1 << 16), build)[0]
+
+
+def mul_mat(w_raw, w_view, x_raw, x_view):
+    """ggml_mul_mat(w, x) of two views of two buffers given as bytes: w_view any weight type (rows nb[1] apart, matrices nb[2] / nb[3] apart, at an offset), x_view F32.
+    A buffer that is no whole number of blocks of its type is lengthened with 0x7f bytes.  Returns the node's dense result, float32 [x.ne[3], x.ne[2], x.ne[1], w.ne[1]]"""
+    def whole(raw, type_):
+        raw, size = _bytes(raw), _BLOCK[type_][0]
+        return raw if raw.nbytes % size == 0 else np.concatenate([raw, np.full(size - raw.nbytes % size, 0x7f, np.uint8)])
+    w_raw, x_raw = whole(w_raw, w_view.type), whole(x_raw, GGML_TYPE_F32)
+    assert x_view.type == GGML_TYPE_F32 and w_view.axes is None
+    xne, _ = x_view.final()
+    shape = (xne[3], xne[2], xne[1], w_view.ne[1])
+
+    def build(base, ctx):
+        w = _view(base, ctx, _parent(base, ctx, w_view.type, w_raw), w_view)
+        x = _view(base, ctx, _parent(base, ctx, GGML_TYPE_F32, x_raw), x_view)
+        out = base.ggml_mul_mat(ctx, w, x)
+        return out, [(out, shape, np.float32)]
+    # the work buffer holds src1 in the weight's vec_dot_type: never more than src1 itself plus a block header per 32 values
+    return _graph(w_raw.nbytes + 3 * x_raw.nbytes + 4 * int(np.prod(shape)) + (1 << 20), build)[0]
 
 
 def soft_max_ext(x, mask, scale, inplace=False):
