@@ -140,6 +140,13 @@ __device__ __forceinline__ f32x4 rms_load4(const float * __restrict__ x, int64_t
     if (aligned) return *(const f32x4 *)(x + 4 * q);
     return f32x4{ x[4*q], x[4*q + 1], x[4*q + 2], x[4*q + 3] };
 }
+// its store side: four floats to y + 4q, one vector store where `aligned`; and f over the four lanes (the norms' output step: nm_out / nm_l2_out, norm_order.h)
+__device__ __forceinline__ void rms_store4(float * y, int64_t q, bool aligned, f32x4 o) {
+    float * yq = y + 4 * q;
+    if (aligned) *(f32x4 *) yq = o;
+    else { yq[0] = o.x; yq[1] = o.y; yq[2] = o.z; yq[3] = o.w; }
+}
+template <class F> __device__ __forceinline__ f32x4 map4(f32x4 v, F && f) { return f32x4{ f(v.x), f(v.y), f(v.z), f(v.w) }; }
 __device__ __forceinline__ double rms_block_sumsq_1024(const float * __restrict__ x, int64_t n, f32x4 first, double * part) {
     const int tid = threadIdx.x;
     const int64_t nq = n >> 2;
@@ -749,6 +756,26 @@ static inline tview tv(const cllm_tensor * t) {
     for (int i = 0; i < 4; i++) { v.ne[i] = t->ne[i]; v.nb[i] = (int64_t) t->nb[i]; }
     return v;
 }
+// Addressing over a tview, each step stated once.  The divisions and their order are what the kernels' index walks have always been.
+struct tcoord { int64_t i0, i1, i2, i3; };
+// row number (over ne[1..3], dimension 1 fastest) -> the row's coordinates, i0 = 0
+__host__ __device__ __forceinline__ tcoord t_row_coord(const tview & v, int64_t row) {
+    return tcoord{ 0, row % v.ne[1], (row / v.ne[1]) % v.ne[2], row / (v.ne[1] * v.ne[2]) };
+}
+// unit number e, dimension 0 fastest, over rows of n0 units and v's ne[1..3] -> its coordinates (a unit: an element, or the block / byte pair a kernel moves at a time)
+__host__ __device__ __forceinline__ tcoord t_unit_coord(int64_t n0, const tview & v, int64_t e) {
+    tcoord c;
+    c.i0 = e % n0;      e /= n0;
+    c.i1 = e % v.ne[1]; e /= v.ne[1];
+    c.i2 = e % v.ne[2]; c.i3 = e / v.ne[2];
+    return c;
+}
+__host__ __device__ __forceinline__ tcoord t_elem_coord(const tview & v, int64_t e) { return t_unit_coord(v.ne[0], v, e); }
+// byte address of coordinates c in v (the coordinates of one tensor address the same element of every tensor of its shape: x in s, y in d)
+__host__ __device__ __forceinline__ char * t_at(const tview & v, const tcoord & c) { return v.data + c.i0*v.nb[0] + c.i1*v.nb[1] + c.i2*v.nb[2] + c.i3*v.nb[3]; }
+__host__ __device__ __forceinline__ char * t_row_at(const tview & v, const tcoord & c) { return v.data + c.i1*v.nb[1] + c.i2*v.nb[2] + c.i3*v.nb[3]; }      // the start of c's row
+// workgroups of 256 threads for n items of a grid-stride loop, at most cap of them
+static inline unsigned grid_1d(int64_t n, int64_t cap) { const int64_t g = (n + 255) / 256; return (unsigned)(g > cap ? cap : g); }
 
 // internal launchers (implemented across the .hip files)
 int launch_quantize_act(hipStream_t st, int kind /* ACT_Q8_0 | ACT_Q8_K | ACT_Q8_1 */, const tview & src1, void * act, size_t act_stride);

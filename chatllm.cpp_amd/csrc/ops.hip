@@ -1,12 +1,32 @@
 // ops.hip -- the non-matmul nodes of one chatllm.cpp forward graph, written for gfx950.
 // Each kernel cites the reference CPU function whose arithmetic (operation order, rounding points,
 // accumulation width) it reproduces; see include/chatllm_hip.h for the op contracts.
+// What the kernels and entries share is stated once: a row's or an element's coordinates and their address (t_row_coord, t_elem_coord, t_at), the 1-D grid (grid_1d)
+// and the norms' store tail (map4, rms_store4) in common.h; the row-wise entries' argument checks in row_op_args below.
 #include "common.h"
 #include "quant_dev.h"
 
 #include <math.h>
 #include <mutex>
 #include <vector>
+
+// The argument checks of the row-wise entries (src and dst of one shape, F32 rows), in the order every one of them has them; `checks` names the steps to run.
+// A row with nb[0] != 4 is CLLM_E_INVALID "shape" to RMS_NORM, SOFT_MAX and ROPE and CLLM_E_UNSUPPORTED to the norms that came after them: both stay as callers rely on them.
+// An empty tensor passes the row limit: it is no launch, and its entry returns CLLM_OK.
+enum { ROW_F32_SHAPE = 1, ROW_DENSE_INVALID = 2, ROW_DENSE_UNSUPPORTED = 4, ROW_LIMIT = 8 };
+static int row_op_args(const char * op, const cllm_tensor * src, const cllm_tensor * dst, int checks) {
+    if (checks & ROW_F32_SHAPE) {
+        if (!src || !dst) FAIL(CLLM_E_INVALID, "%s: null", op);
+        if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "%s: type (F32 only)", op);
+        if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "%s: shape", op);
+    }
+    if ((checks & (ROW_DENSE_INVALID | ROW_DENSE_UNSUPPORTED)) && (src->nb[0] != 4 || dst->nb[0] != 4)) {
+        if (checks & ROW_DENSE_INVALID) FAIL(CLLM_E_INVALID, "%s: shape", op);
+        FAIL(CLLM_E_UNSUPPORTED, "%s: rows must be dense", op);
+    }
+    if ((checks & ROW_LIMIT) && src->ne[0] != 0 && t_nrows(src) > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "%s: more than 2^31 - 1 rows", op);
+    return CLLM_OK;
+}
 
 // ================================================================================================
 // RMS_NORM (+ MUL)      ggml_compute_forward_rms_norm_f32, ggml-cpu/ops.cpp:3710-3759
@@ -15,10 +35,9 @@
 // ================================================================================================
 template <bool MUL>
 __global__ void __launch_bounds__(1024) k_rms_norm(tview s, tview d, const float * __restrict__ w, int64_t w_ne0, float eps) {
-    const int64_t row = blockIdx.x;
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const tcoord c = t_row_coord(s, blockIdx.x);
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
     const int64_t n = s.ne[0];
     __shared__ double part[16];
     const bool aligned = (((uintptr_t) x) & 15) == 0;
@@ -33,9 +52,7 @@ __global__ void __launch_bounds__(1024) k_rms_norm(tview s, tview d, const float
 }
 
 static int rms_norm_impl(void * stream, const cllm_tensor * src, const cllm_tensor * weight, cllm_tensor * dst, float eps) {
-    if (!src || !dst) FAIL(CLLM_E_INVALID, "rms_norm: null");
-    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "rms_norm: type");
-    if (!t_same_shape(src, dst) || src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_INVALID, "rms_norm: shape");
+    if (const int rc = row_op_args("rms_norm", src, dst, ROW_F32_SHAPE | ROW_DENSE_INVALID)) return rc;
     if (weight && (weight->type != CLLM_TYPE_F32 || weight->nb[0] != 4 || weight->ne[0] != src->ne[0] || t_nrows(weight) != 1))
         FAIL(CLLM_E_UNSUPPORTED, "rms_norm_mul: weight must be a dense F32 [ne0] vector");
     const int64_t rows = t_nrows(src);
@@ -60,10 +77,9 @@ extern "C" int cllm_op_rms_norm_mul(void * stream, const cllm_tensor * src, cons
 // the row start is 16-byte aligned.  dst may be src: every store comes after the last barrier of norm_variance, behind every read of the two sums.
 // ================================================================================================
 __global__ void __launch_bounds__(1024) k_norm(tview s, tview d, float eps) {
-    const int64_t row = blockIdx.x;
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const tcoord c = t_row_coord(s, blockIdx.x);
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
     const int64_t n = s.ne[0], ng = n >> 3;
     const int tid = threadIdx.x;
     __shared__ double part[3][16];
@@ -75,27 +91,22 @@ __global__ void __launch_bounds__(1024) k_norm(tview s, tview d, float eps) {
     const float mean = norm_mean(S, A, n, x, &slot[0]);
     const double V = norm_block_var_sum_1024(x, n, aligned, first, mean, part[2]);
     const float scale = nm_scale(norm_variance(V, n, mean, x, &slot[1]), eps);
+    const auto out = [&](float e) { return nm_out(e, mean, scale); };
     norm_g8 v = first;
     for (int64_t g = tid; g < ng; g += 1024) {
         if (g != tid) v = norm_load8(x, g, aligned);
-        const f32x4 lo = { nm_out(v.lo.x, mean, scale), nm_out(v.lo.y, mean, scale), nm_out(v.lo.z, mean, scale), nm_out(v.lo.w, mean, scale) };
-        const f32x4 hi = { nm_out(v.hi.x, mean, scale), nm_out(v.hi.y, mean, scale), nm_out(v.hi.z, mean, scale), nm_out(v.hi.w, mean, scale) };
-        float * yg = y + 8 * g;
-        if (y_aligned) { *(f32x4 *) yg = lo; *(f32x4 *)(yg + 4) = hi; }
-        else { yg[0] = lo.x; yg[1] = lo.y; yg[2] = lo.z; yg[3] = lo.w; yg[4] = hi.x; yg[5] = hi.y; yg[6] = hi.z; yg[7] = hi.w; }
+        const f32x4 lo = map4(v.lo, out), hi = map4(v.hi, out);
+        rms_store4(y, 2 * g, y_aligned, lo); rms_store4(y, 2 * g + 1, y_aligned, hi);
     }
-    if (8 * ng + tid < n) y[8 * ng + tid] = nm_out(x[8 * ng + tid], mean, scale);
+    if (8 * ng + tid < n) y[8 * ng + tid] = out(x[8 * ng + tid]);
 }
 
 extern "C" int cllm_op_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps) {
-    if (!src || !dst) FAIL(CLLM_E_INVALID, "norm: null");
-    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "norm: type (F32 only)");
-    if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "norm: shape");
-    if (!(eps >= 0.0f)) FAIL(CLLM_E_INVALID, "norm: eps must be >= 0");             // (NaN included) the reference asserts eps >= 0, ops.cpp:3661
-    if (src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "norm: rows must be dense");
+    if (const int rc = row_op_args("norm", src, dst, ROW_F32_SHAPE)) return rc;
+    if (!(eps >= 0.0f)) FAIL(CLLM_E_INVALID, "norm: eps must be >= 0");             // (NaN included) the reference asserts eps >= 0, ops.cpp:3661; an unusable eps is reported before a row that is not dense
+    if (const int rc = row_op_args("norm", src, dst, ROW_DENSE_UNSUPPORTED | ROW_LIMIT)) return rc;
     const int64_t rows = t_nrows(src);
     if (rows == 0 || src->ne[0] == 0) return CLLM_OK;
-    if (rows > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "norm: more than 2^31 - 1 rows");
     hipLaunchKernelGGL(k_norm, dim3((unsigned) rows), dim3(1024), 0, (hipStream_t) stream, tv(src), tv(dst), eps);
     LAUNCH_CHECK();
     return CLLM_OK;
@@ -112,10 +123,9 @@ static constexpr int64_t L2_WAVE_ROW_MAX = 512;       // the longest row the wav
 static constexpr int     L2_WAVE_ROWS    = 4;         // rows (waves) per workgroup of that shape
 
 __global__ void __launch_bounds__(1024) k_l2_norm(tview s, tview d, float eps) {
-    const int64_t row = blockIdx.x;
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const tcoord c = t_row_coord(s, blockIdx.x);
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
     const int64_t n = s.ne[0], nq = n >> 2;
     const int tid = threadIdx.x;
     __shared__ double part[16];
@@ -123,48 +133,38 @@ __global__ void __launch_bounds__(1024) k_l2_norm(tview s, tview d, float eps) {
     const f32x4 first = tid < nq ? rms_load4(x, tid, aligned) : f32x4{0, 0, 0, 0};
     const double sum = rms_block_sumsq_1024(x, n, first, part);
     const float scale = l2_block_scale(sum, n, eps, x, part);
+    const auto out = [&](float e) { return nm_l2_out(e, scale); };
     f32x4 v = first;
     for (int64_t q = tid; q < nq; q += 1024) {
         if (q != tid) v = rms_load4(x, q, aligned);
-        const f32x4 o = { nm_l2_out(v.x, scale), nm_l2_out(v.y, scale), nm_l2_out(v.z, scale), nm_l2_out(v.w, scale) };
-        float * yq = y + 4 * q;
-        if (y_aligned) *(f32x4 *) yq = o;
-        else { yq[0] = o.x; yq[1] = o.y; yq[2] = o.z; yq[3] = o.w; }
+        rms_store4(y, q, y_aligned, map4(v, out));
     }
-    if (4 * nq + tid < n) y[4 * nq + tid] = nm_l2_out(x[4 * nq + tid], scale);
+    if (4 * nq + tid < n) y[4 * nq + tid] = out(x[4 * nq + tid]);
 }
 
 __global__ void __launch_bounds__(64 * L2_WAVE_ROWS) k_l2_norm_wave(tview s, tview d, int64_t rows, float eps) {
     const int64_t row = (int64_t) blockIdx.x * L2_WAVE_ROWS + (threadIdx.x >> 6);
     if (row >= rows) return;                                    // a wave past the last row: nothing below waits for it
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const tcoord c = t_row_coord(s, row);
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
     const int64_t n = s.ne[0];
     const int lane = threadIdx.x & 63, nq = (int)(n >> 2);
     const bool y_aligned = (((uintptr_t) y) & 15) == 0;
     const l2_wave_row r = l2_wave_load(x, n, (((uintptr_t) x) & 15) == 0);
     const float scale = l2_wave_scale(r, n, eps, x);
-    auto store4 = [&](int q, f32x4 v) {
-        const f32x4 o = { nm_l2_out(v.x, scale), nm_l2_out(v.y, scale), nm_l2_out(v.z, scale), nm_l2_out(v.w, scale) };
-        float * yq = y + 4 * q;
-        if (y_aligned) *(f32x4 *) yq = o;
-        else { yq[0] = o.x; yq[1] = o.y; yq[2] = o.z; yq[3] = o.w; }
-    };
-    if (lane < nq)      store4(lane, r.v0);
-    if (lane + 64 < nq) store4(lane + 64, r.v1);
-    if (4 * nq + lane < n) y[4 * nq + lane] = nm_l2_out(r.t, scale);
+    const auto out = [&](float e) { return nm_l2_out(e, scale); };
+    if (lane < nq)      rms_store4(y, lane, y_aligned, map4(r.v0, out));
+    if (lane + 64 < nq) rms_store4(y, lane + 64, y_aligned, map4(r.v1, out));
+    if (4 * nq + lane < n) y[4 * nq + lane] = out(r.t);
 }
 
 extern "C" int cllm_op_l2_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, float eps) {
-    if (!src || !dst) FAIL(CLLM_E_INVALID, "l2_norm: null");
-    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "l2_norm: type (F32 only)");
-    if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "l2_norm: shape");
-    if (src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "l2_norm: rows must be dense");
+    if (const int rc = row_op_args("l2_norm", src, dst, ROW_F32_SHAPE | ROW_DENSE_UNSUPPORTED)) return rc;
     if (!(eps >= 0.0f)) FAIL(CLLM_E_INVALID, "l2_norm: eps must be >= 0");          // (NaN included) the reference asserts eps >= 0, ops.cpp:4069
+    if (const int rc = row_op_args("l2_norm", src, dst, ROW_LIMIT)) return rc;
     const int64_t rows = t_nrows(src);
     if (rows == 0 || src->ne[0] == 0) return CLLM_OK;
-    if (rows > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "l2_norm: more than 2^31 - 1 rows");
     if (src->ne[0] <= L2_WAVE_ROW_MAX)
         hipLaunchKernelGGL(k_l2_norm_wave, dim3((unsigned)((rows + L2_WAVE_ROWS - 1) / L2_WAVE_ROWS)), dim3(64 * L2_WAVE_ROWS), 0, (hipStream_t) stream, tv(src), tv(dst), rows, eps);
     else
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(1024) k_group_norm(tview s, tview d, int64_t c
     const int64_t start = g * cpg, end = start + cpg < s.ne[2] ? start + cpg : s.ne[2], step = end - start;
     if (step <= 0) return;                                      // an empty group (C = 5 in 4 groups: the last one) touches nothing; the launcher starts none
     gn_group G;
-    G.x = s.data + start * s.nb[2] + i3 * s.nb[3]; G.y = d.data + start * d.nb[2] + i3 * d.nb[3];
+    G.x = t_at(s, tcoord{0, 0, start, i3}); G.y = t_at(d, tcoord{0, 0, start, i3});
     G.ne0 = s.ne[0]; G.ne1 = s.ne[1]; G.rows = s.ne[1] * step; G.nb1 = s.nb[1]; G.nb2 = s.nb[2]; G.dnb1 = d.nb[1]; G.dnb2 = d.nb[2];
     G.nq = G.ne0 >> 2; G.ipr = G.nq + (G.ne0 & 3); G.items = G.rows * G.ipr; G.N = G.ne0 * G.rows;
     const int tid = threadIdx.x;
@@ -199,23 +199,18 @@ __global__ void __launch_bounds__(1024) k_group_norm(tview s, tview d, int64_t c
     const float mean = gn_mean(S, A, G, &slot[0]);
     const double V = gn_block_var_sum_1024(G, first, mean, part[2]);
     const float scale = nm_scale(gn_variance(V, mean, G, &slot[1]), eps);
+    const auto out = [&](float e) { return nm_out(e, mean, scale); };
     gn_item it = first;
     for (int64_t i = tid; i < G.items; i += 1024) {
         if (i != tid) it = gn_load(G, i);
         float * yr = (float *)(G.y + (it.row % G.ne1) * G.dnb1 + (it.row / G.ne1) * G.dnb2) + it.col;
-        if (it.cnt == 4) {
-            const f32x4 o = { nm_out(it.v.x, mean, scale), nm_out(it.v.y, mean, scale), nm_out(it.v.z, mean, scale), nm_out(it.v.w, mean, scale) };
-            if ((((uintptr_t) yr) & 15) == 0) *(f32x4 *) yr = o;
-            else { yr[0] = o.x; yr[1] = o.y; yr[2] = o.z; yr[3] = o.w; }
-        } else yr[0] = nm_out(it.v.x, mean, scale);
+        if (it.cnt == 4) rms_store4(yr, 0, (((uintptr_t) yr) & 15) == 0, map4(it.v, out));
+        else yr[0] = out(it.v.x);
     }
 }
 
 extern "C" int cllm_op_group_norm(void * stream, const cllm_tensor * src, cllm_tensor * dst, int n_groups, float eps) {
-    if (!src || !dst) FAIL(CLLM_E_INVALID, "group_norm: null");
-    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "group_norm: type (F32 only)");
-    if (!t_same_shape(src, dst)) FAIL(CLLM_E_INVALID, "group_norm: shape");
-    if (src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "group_norm: rows must be dense");
+    if (const int rc = row_op_args("group_norm", src, dst, ROW_F32_SHAPE | ROW_DENSE_UNSUPPORTED)) return rc;
     if (n_groups <= 0) FAIL(CLLM_E_INVALID, "group_norm: n_groups must be > 0");
     if (src->ne[2] > 0x7fffffff || src->ne[3] > 0x7fffffff || src->ne[2] * src->ne[3] > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "group_norm: more than 2^31 - 1 (channel, batch) pairs");
     if (t_nrows(src) == 0 || src->ne[0] == 0) return CLLM_OK;
@@ -260,8 +255,8 @@ __global__ void __launch_bounds__(256) k_rope(tview s, tview d, const int32_t * 
     // rotated pairs
     for (int64_t t = threadIdx.x; t < nh * half; t += blockDim.x) {
         const int64_t h = t / half; const int i = (int)(t % half);
-        const float * x = (const float *)(s.data + h*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-        float *       y = (float *)(d.data + h*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+        const float * x = (const float *) t_at(s, tcoord{0, h, i2, i3});
+        float *       y = (float *) t_at(d, tcoord{0, h, i2, i3});
         const int64_t ic = rope_pair(p.mode, i, half).ic;
         const float c = cache[2*i], sn = cache[2*i + 1];
         const float x0 = x[ic], x1 = x[ic + off];
@@ -273,7 +268,7 @@ __global__ void __launch_bounds__(256) k_rope(tview s, tview d, const int32_t * 
         const int64_t rest = ne0 - p.n_dims;
         for (int64_t t = threadIdx.x; t < nh * rest; t += blockDim.x) {
             const int64_t h = t / rest, i0 = p.n_dims + t % rest;
-            *(float *)(d.data + i0*4 + h*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]) = *(const float *)(s.data + i0*4 + h*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
+            ((float *) t_at(d, tcoord{0, h, i2, i3}))[i0] = ((const float *) t_at(s, tcoord{0, h, i2, i3}))[i0];
         }
     }
 }
@@ -285,9 +280,9 @@ static float rope_corr_dim(int n_dims, int n_ctx_orig, float n_rot, float base) 
 extern "C" int cllm_op_rope(void * stream, const cllm_tensor * src, const cllm_tensor * pos, const cllm_tensor * freq_factors,
                             cllm_tensor * dst, const cllm_rope_params * p) {
     if (!src || !pos || !dst || !p) FAIL(CLLM_E_INVALID, "rope: null");
-    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32 || pos->type != CLLM_TYPE_I32) FAIL(CLLM_E_UNSUPPORTED, "rope: type");
+    if (pos->type != CLLM_TYPE_I32) FAIL(CLLM_E_UNSUPPORTED, "rope: type");
     if (p->mode != 0 && p->mode != 2) FAIL(CLLM_E_UNSUPPORTED, "rope: mode %d", p->mode);
-    if (!t_same_shape(src, dst) || src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_INVALID, "rope: shape");
+    if (const int rc = row_op_args("rope", src, dst, ROW_F32_SHAPE | ROW_DENSE_INVALID)) return rc;
     if (p->n_dims > src->ne[0] || (p->n_dims & 1) || p->n_dims <= 0) FAIL(CLLM_E_INVALID, "rope: n_dims");
     if (pos->ne[0] < src->ne[2]) FAIL(CLLM_E_INVALID, "rope: pos shorter than sequence");
     if (freq_factors && (freq_factors->type != CLLM_TYPE_F32 || freq_factors->ne[0] < p->n_dims / 2)) FAIL(CLLM_E_INVALID, "rope: freq_factors");
@@ -361,10 +356,11 @@ __global__ void __launch_bounds__(256) k_soft_max(tview s, tview d, const char *
     const int64_t row = (int64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nrows = s.ne[1] * s.ne[2] * s.ne[3];
     if (row >= nrows) return;
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
-    const char * mp = mask ? mask + i1*m_nb1 + (i2 % m_ne2)*m_nb2 + (i3 % m_ne3)*m_nb3 : nullptr;
+    const tcoord c = t_row_coord(s, row);
+    const int64_t i1 = c.i1;
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
+    const char * mp = mask ? mask + i1*m_nb1 + (c.i2 % m_ne2)*m_nb2 + (c.i3 % m_ne3)*m_nb3 : nullptr;
     const int64_t n = s.ne[0];
 
     auto val = [&](int64_t i) -> float {
@@ -411,11 +407,11 @@ __global__ void __launch_bounds__(256) k_soft_max_causal_reg(tview s, tview d, f
     const int64_t row = (int64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nrows = s.ne[1] * s.ne[2] * s.ne[3];
     if (row >= nrows) return;
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const tcoord c = t_row_coord(s, row);
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
     const int n = (int) s.ne[0];
-    const int n_vis = n_past + (int) i1 + 1 < n ? n_past + (int) i1 + 1 : n;       // entries >= n_vis are masked
+    const int n_vis = n_past + (int) c.i1 + 1 < n ? n_past + (int) c.i1 + 1 : n;   // entries >= n_vis are masked
     float e[NG][8];
     float mx = -INFINITY;
     // every group's loads are issued before the first value is used (unconditional, clamped to the row's start where the group is masked: inside the
@@ -485,12 +481,11 @@ __global__ void __launch_bounds__(256) k_soft_max_causal_lds(tview s, tview d, f
     __shared__ float red_f[4];
     __shared__ double red_d[1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t row = blockIdx.x;
-    const int64_t i1 = row % s.ne[1], i2 = (row / s.ne[1]) % s.ne[2], i3 = row / (s.ne[1] * s.ne[2]);
-    const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-    float *       y = (float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
+    const tcoord c = t_row_coord(s, blockIdx.x);
+    const float * x = (const float *) t_at(s, c);
+    float *       y = (float *) t_at(d, c);
     const int n = (int) s.ne[0];
-    const int n_vis = n_past + (int) i1 + 1 < n ? n_past + (int) i1 + 1 : n;
+    const int n_vis = n_past + (int) c.i1 + 1 < n ? n_past + (int) c.i1 + 1 : n;
     const int nv_vis = (n_vis + 7) & ~7;                              // n % 8 == 0: whole groups
     float * gsum = sm + n;
     float mx = -INFINITY;
@@ -537,9 +532,7 @@ int launch_soft_max_causal_f16out(hipStream_t st, const tview & sv, float scale,
 }
 
 static int soft_max_impl(void * stream, const cllm_tensor * src, const cllm_tensor * mask, cllm_tensor * dst, float scale, int fused, int n_past) {
-    if (!src || !dst) FAIL(CLLM_E_INVALID, "soft_max: null");
-    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "soft_max: type");
-    if (!t_same_shape(src, dst) || src->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_INVALID, "soft_max: shape");
+    if (const int rc = row_op_args("soft_max", src, dst, ROW_F32_SHAPE | ROW_DENSE_INVALID)) return rc;
     if (mask) {
         if (mask->type != CLLM_TYPE_F32 && mask->type != CLLM_TYPE_F16) FAIL(CLLM_E_UNSUPPORTED, "soft_max: mask type");
         if (mask->ne[0] != src->ne[0] || mask->ne[1] < src->ne[1] || src->ne[2] % mask->ne[2] || src->ne[3] % mask->ne[3]) FAIL(CLLM_E_INVALID, "soft_max: mask shape");
@@ -580,7 +573,7 @@ extern "C" int cllm_op_scale_mask_soft_max(void * stream, const cllm_tensor * sr
 }
 
 // ================================================================================================
-// element-wise family: generic strided, one thread per element of dst, index decomposed over ne[]
+// element-wise family: generic strided, one thread per element of dst (t_elem_coord), src1 broadcast over it
 // ================================================================================================
 enum { EW_DIAG_MASK = 0, EW_SCALE = 1, EW_SILU = 2, EW_ADD = 3, EW_MUL = 4, EW_SILU_MUL = 5, EW_DIV = 6,
        EW_SIGMOID = 7, EW_TANH = 8, EW_RELU = 9, EW_SQR = 10, EW_GELU = 11, EW_GELU_QUICK = 12 };
@@ -603,11 +596,9 @@ template <int OP>
 __global__ void __launch_bounds__(256) k_elementwise(tview a, tview b, tview d, float f0, float f1, int i0p) {
     const int64_t n = d.ne[0] * d.ne[1] * d.ne[2] * d.ne[3];
     for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
-        int64_t r = e;
-        const int64_t i0 = r % d.ne[0]; r /= d.ne[0];
-        const int64_t i1 = r % d.ne[1]; r /= d.ne[1];
-        const int64_t i2 = r % d.ne[2]; const int64_t i3 = r / d.ne[2];
-        const float x = *(const float *)(a.data + i0*a.nb[0] + i1*a.nb[1] + i2*a.nb[2] + i3*a.nb[3]);
+        const tcoord c = t_elem_coord(d, e);
+        const int64_t i0 = c.i0, i1 = c.i1;
+        const float x = *(const float *) t_at(a, c);
         float y;
         if (OP == EW_DIAG_MASK)      y = (i0 > (int64_t) i0p + i1) ? -INFINITY : x;      // ops.cpp:5137-5185
         // ggml_vec_scale_f32 / ggml_vec_mad1_f32 (vec.h:667-712): with a bias the reference build rounds once in every element of a row, the
@@ -624,7 +615,7 @@ __global__ void __launch_bounds__(256) k_elementwise(tview a, tview b, tview d, 
         else if (OP == EW_GELU)      y = gm_gelu_lookup(g_gelu_tab[0], x);                 // ggml_vec_gelu_f32 (vec.h:996-1009)
         else if (OP == EW_GELU_QUICK) y = gm_gelu_quick_lookup(g_gelu_tab[1], x);          // ggml_vec_gelu_quick_f32 (vec.h:1037-1044)
         else {
-            const float z = *(const float *)(b.data + (i0 % b.ne[0])*b.nb[0] + (i1 % b.ne[1])*b.nb[1] + (i2 % b.ne[2])*b.nb[2] + (i3 % b.ne[3])*b.nb[3]);
+            const float z = *(const float *) t_at(b, tcoord{ i0 % b.ne[0], i1 % b.ne[1], c.i2 % b.ne[2], c.i3 % b.ne[3] });
             if (OP == EW_ADD)      y = x + z;
             else if (OP == EW_MUL) y = x * z;
             else if (OP == EW_DIV) y = __fdiv_rn(x, z);                                     // IEEE division (ggml_vec_div_f32)
@@ -633,7 +624,7 @@ __global__ void __launch_bounds__(256) k_elementwise(tview a, tview b, tview d, 
                 y = sl * z;
             }
         }
-        *(float *)(d.data + i0*d.nb[0] + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]) = y;
+        *(float *) t_at(d, c) = y;
     }
 }
 
@@ -645,9 +636,7 @@ static int ew_launch(void * stream, const cllm_tensor * a, const cllm_tensor * b
     if (b) for (int i = 0; i < 4; i++) if (b->ne[i] <= 0 || a->ne[i] % b->ne[i]) FAIL(CLLM_E_INVALID, "%s: src1 not broadcastable", name);
     const int64_t n = t_nelements(d);
     if (n == 0) return CLLM_OK;
-    int64_t grid = (n + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_elementwise<OP>, dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(a), b ? tv(b) : tv(a), tv(d), f0, f1, ip);
+    hipLaunchKernelGGL(k_elementwise<OP>, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t) stream, tv(a), b ? tv(b) : tv(a), tv(d), f0, f1, ip);
     LAUNCH_CHECK();
     return CLLM_OK;
 }
@@ -657,8 +646,6 @@ extern "C" int cllm_op_diag_mask_inf(void * stream, const cllm_tensor * src, cll
 }
 extern "C" int cllm_op_scale(void * stream, const cllm_tensor * src, cllm_tensor * dst, float s, float b) { return ew_launch<EW_SCALE>(stream, src, nullptr, dst, s, b, 0, "scale"); }
 extern "C" int cllm_op_unary(void * stream, int op, const cllm_tensor * src, cllm_tensor * dst) {
-    if (op != CLLM_UNARY_SILU && op != CLLM_UNARY_TANH && op != CLLM_UNARY_RELU && op != CLLM_UNARY_SIGMOID && op != CLLM_UNARY_GELU && op != CLLM_UNARY_GELU_QUICK)
-        FAIL(CLLM_E_UNSUPPORTED, "unary: op %d", op);
     if (src && dst && (src->nb[0] != 4 || dst->nb[0] != 4)) FAIL(CLLM_E_UNSUPPORTED, "unary: rows must be dense");
     switch (op) {
         case CLLM_UNARY_TANH:    return ew_launch<EW_TANH>(stream, src, nullptr, dst, 0, 0, 0, "tanh");
@@ -666,7 +653,8 @@ extern "C" int cllm_op_unary(void * stream, int op, const cllm_tensor * src, cll
         case CLLM_UNARY_SIGMOID: return ew_launch<EW_SIGMOID>(stream, src, nullptr, dst, 0, 0, 0, "sigmoid");
         case CLLM_UNARY_GELU:       if (int rc = gelu_tables_upload()) return rc; return ew_launch<EW_GELU>(stream, src, nullptr, dst, 0, 0, 0, "gelu");
         case CLLM_UNARY_GELU_QUICK: if (int rc = gelu_tables_upload()) return rc; return ew_launch<EW_GELU_QUICK>(stream, src, nullptr, dst, 0, 0, 0, "gelu_quick");
-        default:                 return ew_launch<EW_SILU>(stream, src, nullptr, dst, 0, 0, 0, "silu");
+        case CLLM_UNARY_SILU:    return ew_launch<EW_SILU>(stream, src, nullptr, dst, 0, 0, 0, "silu");
+        default:                 FAIL(CLLM_E_UNSUPPORTED, "unary: op %d", op);
     }
 }
 extern "C" int cllm_op_sqr(void * stream, const cllm_tensor * src, cllm_tensor * dst) {
@@ -685,11 +673,11 @@ extern "C" int cllm_op_silu_mul(void * stream, const cllm_tensor * g, const cllm
 __global__ void __launch_bounds__(256) k_sum_rows(tview s, tview d) {
     const int64_t rows = s.ne[1] * s.ne[2] * s.ne[3];
     for (int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t) gridDim.x * blockDim.x) {
-        const int64_t i1 = r % s.ne[1], i2 = (r / s.ne[1]) % s.ne[2], i3 = r / (s.ne[1] * s.ne[2]);
-        const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
+        const tcoord c = t_row_coord(s, r);
+        const float * x = (const float *) t_at(s, c);
         double sum = 0.0;
         for (int64_t i = 0; i < s.ne[0]; i++) sum += (double) x[i];
-        *(float *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]) = (float) sum;
+        *(float *) t_at(d, c) = (float) sum;
     }
 }
 extern "C" int cllm_op_sum_rows(void * stream, const cllm_tensor * src, cllm_tensor * dst) {
@@ -698,8 +686,7 @@ extern "C" int cllm_op_sum_rows(void * stream, const cllm_tensor * src, cllm_ten
     if (dst->ne[0] != 1 || dst->ne[1] != src->ne[1] || dst->ne[2] != src->ne[2] || dst->ne[3] != src->ne[3]) FAIL(CLLM_E_INVALID, "sum_rows: shape");
     const int64_t rows = src->ne[1] * src->ne[2] * src->ne[3];
     if (rows == 0) return CLLM_OK;
-    int64_t grid = (rows + 255) / 256; if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(k_sum_rows, dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst));
+    hipLaunchKernelGGL(k_sum_rows, dim3(grid_1d(rows, 4096)), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst));
     LAUNCH_CHECK();
     return CLLM_OK;
 }
@@ -710,10 +697,8 @@ __global__ void __launch_bounds__(256) k_top_k(tview s, tview d, int k) {
     const int64_t rows = s.ne[1] * s.ne[2] * s.ne[3];
     const int n = (int) s.ne[0];
     for (int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t) gridDim.x * blockDim.x) {
-        const int64_t i1 = r % s.ne[1], i2 = (r / s.ne[1]) % s.ne[2], i3 = r / (s.ne[1] * s.ne[2]);
-        const float * x = (const float *)(s.data + i1*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-        int32_t * out = (int32_t *)(d.data + i1*d.nb[1] + i2*d.nb[2] + i3*d.nb[3]);
-        top_k_row(x, n, k, out);
+        const tcoord c = t_row_coord(s, r);
+        top_k_row((const float *) t_at(s, c), n, k, (int32_t *) t_at(d, c));
     }
 }
 extern "C" int cllm_op_top_k(void * stream, const cllm_tensor * src, cllm_tensor * dst) {
@@ -724,8 +709,7 @@ extern "C" int cllm_op_top_k(void * stream, const cllm_tensor * src, cllm_tensor
     if (src->ne[0] > 4096) FAIL(CLLM_E_UNSUPPORTED, "top_k: rows of %lld values", (long long) src->ne[0]);
     const int64_t rows = src->ne[1] * src->ne[2] * src->ne[3];
     if (rows == 0) return CLLM_OK;
-    int64_t grid = (rows + 255) / 256; if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(k_top_k, dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), (int) k);
+    hipLaunchKernelGGL(k_top_k, dim3(grid_1d(rows, 4096)), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), (int) k);
     LAUNCH_CHECK();
     return CLLM_OK;
 }
@@ -764,8 +748,7 @@ extern "C" int cllm_op_moe_combine(void * stream, const cllm_tensor * experts, c
         experts->nb[0] != 4 || probs->nb[0] != 4 || dst->nb[0] != 4 || (resid && (resid->ne[0] != H || resid->ne[1] != T || resid->nb[0] != 4)))
         FAIL(CLLM_E_INVALID, "moe_combine: shapes");
     if (H * T == 0) return CLLM_OK;
-    int64_t grid = (H * T + 255) / 256; if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_moe_combine, dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(experts), tv(probs), tv(ids), resid ? tv(resid) : tv(dst), tv(dst), (int) k, resid ? 1 : 0);
+    hipLaunchKernelGGL(k_moe_combine, dim3(grid_1d(H * T, 8192)), dim3(256), 0, (hipStream_t) stream, tv(experts), tv(probs), tv(ids), resid ? tv(resid) : tv(dst), tv(dst), (int) k, resid ? 1 : 0);
     LAUNCH_CHECK();
     return CLLM_OK;
 }
@@ -773,19 +756,21 @@ extern "C" int cllm_op_moe_combine(void * stream, const cllm_tensor * experts, c
 // ================================================================================================
 // SET_ROWS (K-cache write)   ggml_compute_forward_set_rows_f32, ops.cpp:4892-4940
 // ================================================================================================
+// the destination row of the source row at c: the index tensor [ne1, ...] is broadcast over dimensions 2 and 3 of the source
+template <typename IDX>
+__device__ __forceinline__ int64_t set_rows_row(const tview & idx, const tcoord & c) {
+    return (int64_t) *(const IDX *) t_at(idx, tcoord{ c.i1, c.i2 % idx.ne[1], c.i3 % idx.ne[2], 0 });
+}
 template <typename IDX, bool F16>
 __global__ void __launch_bounds__(256) k_set_rows(tview s, tview idx, tview d) {
     const int64_t n = s.ne[0] * s.ne[1] * s.ne[2] * s.ne[3];
     for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
-        int64_t r = e;
-        const int64_t c  = r % s.ne[0]; r /= s.ne[0];
-        const int64_t i  = r % s.ne[1]; r /= s.ne[1];
-        const int64_t i2 = r % s.ne[2]; const int64_t i3 = r / s.ne[2];
-        const int64_t row = (int64_t) *(const IDX *)(idx.data + i*idx.nb[0] + (i2 % idx.ne[1])*idx.nb[1] + (i3 % idx.ne[2])*idx.nb[2]);
+        const tcoord c = t_elem_coord(s, e);
+        const int64_t row = set_rows_row<IDX>(idx, c);
         if (row < 0 || row >= d.ne[1]) continue;     // the CPU asserts; never write out of bounds
-        const float v = *(const float *)(s.data + c*4 + i*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
-        char * dp = d.data + row*d.nb[1] + i2*d.nb[2] + i3*d.nb[3];
-        if (F16) ((uint16_t *) dp)[c] = f2h(v); else ((float *) dp)[c] = v;
+        const float v = ((const float *) t_row_at(s, c))[c.i0];
+        char * dp = t_at(d, tcoord{0, row, c.i2, c.i3});
+        if (F16) ((uint16_t *) dp)[c.i0] = f2h(v); else ((float *) dp)[c.i0] = v;
     }
 }
 // Q8_0 rows (--cache_dtype q8_0, src/layers.cpp:2925-2945): from_float of the CPU traits = quantize_row_q8_0 (x86 branch), 8 lanes per 32-block
@@ -795,22 +780,22 @@ __global__ void __launch_bounds__(256) k_set_rows_q8_0(tview s, tview idx, tview
     const int sub = threadIdx.x & 7;
     for (int64_t g0 = ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 3; g0 - ((threadIdx.x & 63) >> 3) < nblk; g0 += ((int64_t) gridDim.x * blockDim.x) >> 3) {
         const bool live = g0 < nblk;                            // whole waves stay in the loop: the 8-lane reductions read their neighbours by DPP
-        int64_t r = live ? g0 : nblk - 1;
-        const int64_t blk = r % nb; r /= nb;
-        const int64_t i  = r % s.ne[1]; r /= s.ne[1];
-        const int64_t i2 = r % s.ne[2]; const int64_t i3 = r / s.ne[2];
-        const int64_t row = (int64_t) *(const IDX *)(idx.data + i*idx.nb[0] + (i2 % idx.ne[1])*idx.nb[1] + (i3 % idx.ne[2])*idx.nb[2]);
-        const f32x4 v = *(const f32x4 *)(s.data + (blk * 32 + sub * 4) * 4 + i*s.nb[1] + i2*s.nb[2] + i3*s.nb[3]);
+        const tcoord c = t_unit_coord(nb, s, live ? g0 : nblk - 1);      // i0: the 32-block of the row
+        const int64_t blk = c.i0, row = set_rows_row<IDX>(idx, c);
+        const f32x4 v = *(const f32x4 *)(t_row_at(s, c) + (blk * 32 + sub * 4) * 4);
         float dd; int ss;
         const uint32_t p = quant4_q8_0<false, true>(v, &dd, &ss);      // SAT: an inverse scale that overflows gives 32 quants of -128, as the CPU's saturating packs do
         if (!live || row < 0 || row >= d.ne[1]) continue;
-        char * dp = d.data + row*d.nb[1] + i2*d.nb[2] + i3*d.nb[3] + blk * 34;
+        char * dp = t_at(d, tcoord{0, row, c.i2, c.i3}) + blk * 34;
         if (sub == 0) *(uint16_t *) dp = f2h(dd);
         *(uint16_t *)(dp + 2 + sub * 4) = (uint16_t) p; *(uint16_t *)(dp + 4 + sub * 4) = (uint16_t)(p >> 16);
     }
 }
+// leaf(IDX()) with the element type of an index tensor that its caller has checked to be I32 or I64
+template <class Leaf> static inline void with_idx_type(int type, Leaf && leaf) { if (type == CLLM_TYPE_I64) leaf(int64_t()); else leaf(int32_t()); }
 extern "C" int cllm_op_set_rows(void * stream, const cllm_tensor * src, const cllm_tensor * idx, cllm_tensor * dst) {
     if (!src || !idx || !dst) FAIL(CLLM_E_INVALID, "set_rows: null");
+    hipStream_t st = (hipStream_t) stream;
     if (src->type == CLLM_TYPE_F32 && dst->type == CLLM_TYPE_Q8_0) {
         if (idx->type != CLLM_TYPE_I32 && idx->type != CLLM_TYPE_I64) FAIL(CLLM_E_UNSUPPORTED, "set_rows: index type");
         if (dst->ne[0] != src->ne[0] || dst->ne[2] != src->ne[2] || dst->ne[3] != src->ne[3] || src->nb[0] != 4 || dst->nb[0] != 34 || src->ne[0] % 32) FAIL(CLLM_E_INVALID, "set_rows: shape");
@@ -818,9 +803,7 @@ extern "C" int cllm_op_set_rows(void * stream, const cllm_tensor * src, const cl
         if ((((uintptr_t) src->data | src->nb[1] | src->nb[2] | src->nb[3]) & 15) || (((uintptr_t) dst->data | dst->nb[1] | dst->nb[2] | dst->nb[3]) & 1)) FAIL(CLLM_E_UNSUPPORTED, "set_rows: alignment");
         const int64_t nblk = t_nelements(src) / 32;
         if (nblk == 0) return CLLM_OK;
-        int64_t grid = (nblk * 8 + 255) / 256; if (grid > 8192) grid = 8192;
-        if (idx->type == CLLM_TYPE_I64) hipLaunchKernelGGL((k_set_rows_q8_0<int64_t>), dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(src), tv(idx), tv(dst));
-        else                            hipLaunchKernelGGL((k_set_rows_q8_0<int32_t>), dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(src), tv(idx), tv(dst));
+        with_idx_type(idx->type, [&](auto i) { hipLaunchKernelGGL((k_set_rows_q8_0<decltype(i)>), dim3(grid_1d(nblk * 8, 8192)), dim3(256), 0, st, tv(src), tv(idx), tv(dst)); });
         LAUNCH_CHECK();
         return CLLM_OK;
     }
@@ -830,13 +813,10 @@ extern "C" int cllm_op_set_rows(void * stream, const cllm_tensor * src, const cl
     if (idx->ne[0] != src->ne[1] || src->ne[2] % idx->ne[1] || src->ne[3] % idx->ne[2]) FAIL(CLLM_E_INVALID, "set_rows: index shape");
     const int64_t n = t_nelements(src);
     if (n == 0) return CLLM_OK;
-    int64_t grid = (n + 255) / 256; if (grid > 8192) grid = 8192;
-    hipStream_t st = (hipStream_t) stream;
-    const bool f16 = dst->type == CLLM_TYPE_F16, i64 = idx->type == CLLM_TYPE_I64;
-    if (f16 && !i64)       hipLaunchKernelGGL((k_set_rows<int32_t, true>),  dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(idx), tv(dst));
-    else if (f16 && i64)   hipLaunchKernelGGL((k_set_rows<int64_t, true>),  dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(idx), tv(dst));
-    else if (!f16 && !i64) hipLaunchKernelGGL((k_set_rows<int32_t, false>), dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(idx), tv(dst));
-    else                   hipLaunchKernelGGL((k_set_rows<int64_t, false>), dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(idx), tv(dst));
+    with_idx_type(idx->type, [&](auto i) {
+        if (dst->type == CLLM_TYPE_F16) hipLaunchKernelGGL((k_set_rows<decltype(i), true>),  dim3(grid_1d(n, 8192)), dim3(256), 0, st, tv(src), tv(idx), tv(dst));
+        else                            hipLaunchKernelGGL((k_set_rows<decltype(i), false>), dim3(grid_1d(n, 8192)), dim3(256), 0, st, tv(src), tv(idx), tv(dst));
+    });
     LAUNCH_CHECK();
     return CLLM_OK;
 }
@@ -848,35 +828,20 @@ template <typename TS, typename TD>
 __global__ void __launch_bounds__(256) k_cpy(tview s, tview d) {
     const int64_t n = s.ne[0] * s.ne[1] * s.ne[2] * s.ne[3];
     for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
-        int64_t r = e;
-        const int64_t s0 = r % s.ne[0]; r /= s.ne[0];
-        const int64_t s1 = r % s.ne[1]; r /= s.ne[1];
-        const int64_t s2 = r % s.ne[2]; const int64_t s3 = r / s.ne[2];
-        r = e;
-        const int64_t d0 = r % d.ne[0]; r /= d.ne[0];
-        const int64_t d1 = r % d.ne[1]; r /= d.ne[1];
-        const int64_t d2 = r % d.ne[2]; const int64_t d3 = r / d.ne[2];
-        const TS v = *(const TS *)(s.data + s0*s.nb[0] + s1*s.nb[1] + s2*s.nb[2] + s3*s.nb[3]);
+        const TS v = *(const TS *) t_at(s, t_elem_coord(s, e));
         TD o;
         if constexpr (sizeof(TS) == sizeof(TD)) o = (TD) v;
         else if constexpr (sizeof(TS) == 4) o = f2h(v);          // F32 -> F16, RNE
         else o = h2f(v);                                         // F16 -> F32
-        *(TD *)(d.data + d0*d.nb[0] + d1*d.nb[1] + d2*d.nb[2] + d3*d.nb[3]) = o;
+        *(TD *) t_at(d, t_elem_coord(d, e)) = o;
     }
 }
 // same quantized type on both sides (CONT of the permuted Q8_0 K-cache view, src/layers.cpp:3144-3146): whole rows move, 2 bytes per thread step
 __global__ void __launch_bounds__(256) k_cpy_qrows(tview s, tview d, int row_bytes) {
     const int64_t h = row_bytes / 2, n = h * s.ne[1] * s.ne[2] * s.ne[3];
     for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
-        int64_t r = e;
-        const int64_t c = r % h; r /= h;
-        const int64_t row = r;
-        const int64_t s1 = r % s.ne[1]; r /= s.ne[1];
-        const int64_t s2 = r % s.ne[2]; const int64_t s3 = r / s.ne[2];
-        r = row;
-        const int64_t d1 = r % d.ne[1]; r /= d.ne[1];
-        const int64_t d2 = r % d.ne[2]; const int64_t d3 = r / d.ne[2];
-        *(uint16_t *)(d.data + c*2 + d1*d.nb[1] + d2*d.nb[2] + d3*d.nb[3]) = *(const uint16_t *)(s.data + c*2 + s1*s.nb[1] + s2*s.nb[2] + s3*s.nb[3]);
+        const tcoord cs = t_unit_coord(h, s, e), cd = t_unit_coord(h, d, e);      // i0: the byte pair of the row, the same on both sides
+        ((uint16_t *) t_row_at(d, cd))[cd.i0] = ((const uint16_t *) t_row_at(s, cs))[cs.i0];
     }
 }
 extern "C" int cllm_op_cpy(void * stream, const cllm_tensor * src, cllm_tensor * dst) {
@@ -887,8 +852,7 @@ extern "C" int cllm_op_cpy(void * stream, const cllm_tensor * src, cllm_tensor *
         if ((((uintptr_t) src->data | src->nb[1] | src->nb[2] | src->nb[3] | (uintptr_t) dst->data | dst->nb[1] | dst->nb[2] | dst->nb[3]) & 1)) FAIL(CLLM_E_UNSUPPORTED, "cpy: alignment");
         const int64_t n = (int64_t)(rb / 2) * src->ne[1] * src->ne[2] * src->ne[3];
         if (n == 0) return CLLM_OK;
-        int64_t grid = (n + 255) / 256; if (grid > 16384) grid = 16384;
-        hipLaunchKernelGGL(k_cpy_qrows, dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), (int) rb);
+        hipLaunchKernelGGL(k_cpy_qrows, dim3(grid_1d(n, 16384)), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), (int) rb);
         LAUNCH_CHECK();
         return CLLM_OK;
     }
@@ -899,12 +863,12 @@ extern "C" int cllm_op_cpy(void * stream, const cllm_tensor * src, cllm_tensor *
     if (t_nelements(src) != t_nelements(dst)) FAIL(CLLM_E_INVALID, "cpy: element count");
     const int64_t n = t_nelements(src);
     if (n == 0) return CLLM_OK;
-    int64_t grid = (n + 255) / 256; if (grid > 16384) grid = 16384;
+    const dim3 grid(grid_1d(n, 16384));
     hipStream_t st = (hipStream_t) stream;
-    if (s32 && d32)      hipLaunchKernelGGL((k_cpy<uint32_t, uint32_t>), dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(dst));
-    else if (s16 && d16) hipLaunchKernelGGL((k_cpy<uint16_t, uint16_t>), dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(dst));
-    else if (s32 && d16) hipLaunchKernelGGL((k_cpy<float, uint16_t>),    dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(dst));
-    else                 hipLaunchKernelGGL((k_cpy<uint16_t, float>),    dim3((unsigned) grid), dim3(256), 0, st, tv(src), tv(dst));
+    if (s32 && d32)      hipLaunchKernelGGL((k_cpy<uint32_t, uint32_t>), grid, dim3(256), 0, st, tv(src), tv(dst));
+    else if (s16 && d16) hipLaunchKernelGGL((k_cpy<uint16_t, uint16_t>), grid, dim3(256), 0, st, tv(src), tv(dst));
+    else if (s32 && d16) hipLaunchKernelGGL((k_cpy<float, uint16_t>),    grid, dim3(256), 0, st, tv(src), tv(dst));
+    else                 hipLaunchKernelGGL((k_cpy<uint16_t, float>),    grid, dim3(256), 0, st, tv(src), tv(dst));
     LAUNCH_CHECK();
     return CLLM_OK;
 }
@@ -916,14 +880,11 @@ extern "C" int cllm_op_cpy(void * stream, const cllm_tensor * src, cllm_tensor *
 __global__ void __launch_bounds__(256) k_get_rows(int type, tview s, tview idx, tview d) {
     const int64_t n = d.ne[0] * d.ne[1] * d.ne[2] * d.ne[3];
     for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
-        int64_t r = e;
-        const int64_t c   = r % d.ne[0]; r /= d.ne[0];
-        const int64_t i10 = r % d.ne[1]; r /= d.ne[1];
-        const int64_t i11 = r % d.ne[2]; const int64_t i12 = r / d.ne[2];
-        const int64_t row = *(const int32_t *)(idx.data + i10*idx.nb[0] + i11*idx.nb[1] + i12*idx.nb[2]);
+        const tcoord c = t_elem_coord(d, e);
+        const int64_t row = *(const int32_t *) t_at(idx, tcoord{c.i1, c.i2, c.i3, 0});
         float v = 0.0f;
-        if (row >= 0 && row < s.ne[1]) v = dequant_elem(type, s.data + row*s.nb[1] + i11*s.nb[2] + i12*s.nb[3], c);
-        *(float *)(d.data + c*4 + i10*d.nb[1] + i11*d.nb[2] + i12*d.nb[3]) = v;
+        if (row >= 0 && row < s.ne[1]) v = dequant_elem(type, t_at(s, tcoord{0, row, c.i2, c.i3}), c.i0);
+        ((float *) t_row_at(d, c))[c.i0] = v;
     }
 }
 extern "C" int cllm_op_get_rows(void * stream, const cllm_tensor * src, const cllm_tensor * idx, cllm_tensor * dst) {
@@ -933,8 +894,7 @@ extern "C" int cllm_op_get_rows(void * stream, const cllm_tensor * src, const cl
     if (dst->ne[0] != src->ne[0] || dst->ne[1] != idx->ne[0] || dst->ne[2] != idx->ne[1] || dst->ne[3] != idx->ne[2] || dst->nb[0] != 4) FAIL(CLLM_E_INVALID, "get_rows: shape");
     const int64_t n = t_nelements(dst);
     if (n == 0) return CLLM_OK;
-    int64_t grid = (n + 255) / 256; if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_get_rows, dim3((unsigned) grid), dim3(256), 0, (hipStream_t) stream, src->type, tv(src), tv(idx), tv(dst));
+    hipLaunchKernelGGL(k_get_rows, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t) stream, src->type, tv(src), tv(idx), tv(dst));
     LAUNCH_CHECK();
     return CLLM_OK;
 }

@@ -10,6 +10,7 @@ import pytest
 
 import ref_l2_group_norm as G
 import ref_norm as N
+from permuted_views import permuted
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +112,19 @@ def test_strided_rows_channels_and_batches(gpu):
     got = whole.numpy().reshape(wide.shape)
     N.assert_same_words(got[:2, :4, :3, :30], want, "strided, in place")
     assert np.array_equal(got[~inside], wide[~inside])
+
+
+def test_a_permuted_padded_view(gpu):
+    """[5, 3, 4, 2] in 2 groups with padded rows and nb[2] > nb[3] (tests/permuted_views.py), another padding on the destination: the reference's words over the
+    gathered values"""
+    def make():
+        x = G.random_tensor([5, 3, 4, 2], 905)
+        return x, G.group_norm(x, 2, EPS)
+    x, want = shared(("permuted",), make)
+    src, _ = permuted(gpu, x, 3)
+    dst, read = permuted(gpu, np.zeros_like(x), 6)
+    gpu.ops.group_norm(src, 2, EPS, dst=dst)
+    N.assert_same_words(read(), want, "permuted, padded")
 
 
 @pytest.mark.parametrize("ne0", [33, 1028])

@@ -9,6 +9,7 @@ import pytest
 
 import ref_l2_group_norm as G
 import ref_norm as N
+from permuted_views import permuted
 
 pytestmark = pytest.mark.gpu
 
@@ -110,6 +111,20 @@ def test_strided_rows(gpu, ne0, pad):
     got = whole.numpy()
     N.assert_same_words(got[:, :ne0], want, "strided, in place")
     assert np.array_equal(got[:, ne0:], wide[:, ne0:])
+
+
+@pytest.mark.parametrize("ne0", [9, 521])
+def test_a_permuted_padded_view(gpu, ne0):
+    """[ne0, 3, 2, 2] with padded rows and nb[2] > nb[3] (tests/permuted_views.py), another padding on the destination: the reference's words over the gathered values.
+    9: a wave per row; 521: a workgroup per row"""
+    def make():
+        x = N.random_rows(12, ne0, 709 + ne0).reshape(2, 2, 3, ne0)
+        return x, G.l2_norm(x, EPS)
+    x, want = shared(("permuted", ne0), make)
+    src, _ = permuted(gpu, x, 3)
+    dst, read = permuted(gpu, np.zeros_like(x), 7)
+    gpu.ops.l2_norm(src, EPS, dst=dst)
+    N.assert_same_words(read(), want, "permuted, padded")
 
 
 @pytest.mark.parametrize("ne0", [33, 128, 1028])

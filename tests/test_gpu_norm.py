@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import ref_norm as N
+from permuted_views import permuted
 
 pytestmark = pytest.mark.gpu
 
@@ -82,6 +83,18 @@ def test_strided_rows(gpu):
     got = whole.numpy()
     N.assert_same_words(got[:, :33], want, "strided, in place")
     assert np.array_equal(got[:, 33:], wide[:, 33:])
+
+
+def test_a_permuted_padded_view(gpu):
+    """[9, 3, 2, 2] with padded rows and nb[2] > nb[3] (tests/permuted_views.py), another padding on the destination: the reference's words over the gathered values"""
+    def make():
+        x = N.random_rows(12, 9, 509).reshape(2, 2, 3, 9)
+        return x, N.norm(x, EPS)
+    x, want = shared(("permuted",), make)
+    src, _ = permuted(gpu, x, 3)
+    dst, read = permuted(gpu, np.zeros_like(x), 7)
+    gpu.ops.norm(src, EPS, dst=dst)
+    N.assert_same_words(read(), want, "permuted, padded")
 
 
 @pytest.mark.parametrize("ne0", [33, 1028])

@@ -13,6 +13,7 @@ import pytest
 import oracle as O
 from conftest import prefill_mode
 from attn_long_model import boundary_rows
+from permuted_views import permuted
 from synth_helpers import rand_blocks, rms_boundary_rows
 
 pytestmark = pytest.mark.gpu
@@ -370,6 +371,20 @@ def test_rms_norm(gpu, n0, rows):
     assert np.array_equal(got2.view(np.uint32), want2.view(np.uint32))
 
 
+def test_rms_norm_permuted_padded_view(gpu):
+    """[9, 3, 2, 2] with padded rows and nb[2] > nb[3] (tests/permuted_views.py), another padding on the destination: the words of the oracle over the gathered values"""
+    x = rng.standard_normal((2, 2, 3, 9)).astype(np.float32)
+    w = (1 + 0.1 * rng.standard_normal(9)).astype(np.float32)
+    want = np.zeros_like(x)
+    O.rms_norm(O.tensor(x, O.F32, [9, 3, 2, 2]), O.tensor(want, O.F32, [9, 3, 2, 2]), 1e-5)
+    src, _ = permuted(gpu, x, 3)
+    dst, read = permuted(gpu, np.zeros_like(x), 7)
+    gpu.ops.rms_norm(src, 1e-5, dst=dst)
+    assert np.array_equal(read().view(np.uint32), want.view(np.uint32))
+    gpu.ops.rms_norm_mul(src, gpu.Tensor.from_numpy(w), 1e-5, dst=dst)
+    assert np.array_equal(read().view(np.uint32), (want * w).view(np.uint32))
+
+
 @pytest.mark.parametrize("n0", [4096, 1000, 8192, 14336])
 def test_rms_norm_rows_on_a_rounding_boundary(gpu, n0):
     """rows whose mean of squares lies on a float rounding boundary (tests/synth_helpers.rms_boundary_rows): the float the reference rounds it to depends on the
@@ -528,6 +543,28 @@ def test_scale_mask_soft_max_equals_three_nodes(gpu, qlen, n_past):
     assert np.array_equal(fused == 0, want == 0)      # the causal structure is exact
 
 
+@pytest.mark.parametrize("n0", [9, 40, 512, 8200])
+def test_soft_max_permuted_padded_view(gpu, n0):
+    """[n0, 3, 2, 2] with padded rows and nb[2] > nb[3] (tests/permuted_views.py), another padding on the destination: the words of the oracle over the gathered values.
+    9: the leftover loop alone; 40: the groups of 8; plain and fused with the causal mask (i1 decides what a row sees).  512 and 8200, fused: the register-resident
+    and the LDS kernel"""
+    x = (rng.standard_normal((2, 2, 3, n0)) * 3).astype(np.float32)
+    ne, n_past, s = [n0, 3, 2, 2], n0 - 3, 0.125
+    src, _ = permuted(gpu, x, 4)
+    dst, read = permuted(gpu, np.zeros_like(x), 8)
+    want = np.zeros_like(x)
+    if n0 < 512:
+        O.soft_max(O.tensor(x, O.F32, ne), None, O.tensor(want, O.F32, ne))
+        gpu.ops.soft_max(src, dst=dst)
+        assert np.array_equal(read().view(np.uint32), want.view(np.uint32))
+    Wo = O.tensor(want, O.F32, ne)
+    O.scale(O.tensor(x, O.F32, ne), Wo, s)
+    O.diag_mask_inf(Wo, Wo, n_past)
+    O.soft_max(Wo, None, Wo)
+    gpu.ops.scale_mask_soft_max(src, s, n_past, dst=dst)
+    assert np.array_equal(read().view(np.uint32), want.view(np.uint32))
+
+
 def test_diag_mask_scale_add_mul_silu(gpu):
     x = (rng.standard_normal((2, 5, 61)) * 4).astype(np.float32)
     b = rng.standard_normal((1, 1, 61)).astype(np.float32)
@@ -634,6 +671,22 @@ def test_moe_router_ops_bit_exact(gpu, n0, n1, n2, k):
     wantd = np.zeros_like(x)
     O.div(O.tensor(x, O.F32, [n0, n1, n2]), O.tensor(y, O.F32, [1, n1, n2]), O.tensor(wantd, O.F32, [n0, n1, n2]))
     assert np.array_equal(ops.div(dx, T.from_numpy(y)).numpy().reshape(x.shape).view(np.uint32), wantd.view(np.uint32))
+
+
+def test_sum_rows_and_top_k_permuted_padded_view(gpu):
+    """[9, 3, 2, 2] with padded rows and nb[2] > nb[3] (tests/permuted_views.py), another padding on the destinations: the oracle's words over the gathered values"""
+    x = rng.standard_normal((2, 2, 3, 9)).astype(np.float32)
+    src, _ = permuted(gpu, x, 3)
+    want = np.zeros((2, 2, 3, 1), np.float32)
+    O.sum_rows(O.tensor(x, O.F32, [9, 3, 2, 2]), O.tensor(want, O.F32, [1, 3, 2, 2]))
+    dst, read = permuted(gpu, np.zeros_like(want), 5)
+    gpu.ops.sum_rows(src, dst=dst)
+    assert np.array_equal(read().view(np.uint32), want.view(np.uint32))
+    wantk = np.zeros((2, 2, 3, 4), np.int32)
+    O.top_k(O.tensor(x, O.F32, [9, 3, 2, 2]), O.tensor(wantk, O.I32, [4, 3, 2, 2]))
+    dstk, readk = permuted(gpu, np.zeros_like(wantk), 5)
+    gpu.ops.top_k(src, 4, dst=dstk)
+    assert np.array_equal(readk(), wantk)
 
 
 @pytest.mark.parametrize("t,K,F,E,k", [(O.Q4_K, 4096, 1024, 8, 2), (O.Q8_0, 512, 264, 4, 2), (O.Q4_0, 1024, 512, 8, 3), (O.Q4_1, 256, 64, 8, 2)])
