@@ -298,15 +298,17 @@ template <class... P> static bool aligned16(P... p) { return ((... | (uintptr_t)
 
 static int check_mm(const cllm_tensor * src0, const cllm_tensor * src1, const cllm_tensor * dst, const char * name) {
     if (!src0 || !src1 || !dst) FAIL(CLLM_E_INVALID, "%s: null tensor", name);
-    if (src1->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "%s: src1/dst must be F32", name);
+    // an F16 src1 is src0's vec_dot_type only when src0 is F16: the reference then reads it in place (ggml-cpu.c:1170), the second operand of a convolution's mat-mul
+    const bool x16 = src1->type == CLLM_TYPE_F16 && src0->type == CLLM_TYPE_F16;
+    if ((src1->type != CLLM_TYPE_F32 && !x16) || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "%s: src1/dst must be F32 (src1 may be F16 with an F16 src0)", name);
     if (!is_quant(src0->type) && src0->type != CLLM_TYPE_F16 && src0->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "%s: src0 type %d", name, src0->type);
     if (src0->ne[0] != src1->ne[0]) FAIL(CLLM_E_INVALID, "%s: K mismatch %lld vs %lld", name, (long long) src0->ne[0], (long long) src1->ne[0]);
-    if (src0->nb[0] != cllm_type_size(src0->type) || src1->nb[0] != 4 || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "%s: rows must be dense", name);
+    if (src0->nb[0] != cllm_type_size(src0->type) || src1->nb[0] != cllm_type_size(src1->type) || dst->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "%s: rows must be dense", name);
     if (src0->ne[0] % cllm_blck_size(src0->type)) FAIL(CLLM_E_INVALID, "%s: K not a multiple of the block size", name);
     if (src0->type == CLLM_TYPE_Q4_1 && !rows_aligned(src0)) FAIL(CLLM_E_UNSUPPORTED, "%s: Q4_1 rows must be %d-byte aligned", name, wtype_row_align(src0->type));
     // dst rows and planes are whole floats apart in every kernel; the float kernels load src0 / src1 element by element (the quantized ones: mm_wdata_and_alignment, kq_check)
     if (((uintptr_t) dst->data | dst->nb[1] | dst->nb[2] | dst->nb[3]) % 4) FAIL(CLLM_E_INVALID, "%s: dst stride", name);
-    if (!is_quant(src0->type) && (!rows_aligned(src0) || ((uintptr_t) src1->data | src1->nb[1] | src1->nb[2] | src1->nb[3]) % 4))
+    if (!is_quant(src0->type) && (!rows_aligned(src0) || ((uintptr_t) src1->data | src1->nb[1] | src1->nb[2] | src1->nb[3]) % cllm_type_size(src1->type)))
         FAIL(CLLM_E_UNSUPPORTED, "%s: float operands must be aligned to their elements", name);
     return CLLM_OK;
 }
@@ -371,7 +373,7 @@ extern "C" int cllm_op_mul_mat(void * stream, const cllm_tensor * src0, const cl
     hipStream_t st = (hipStream_t) stream;
     if (src0->ne[0] == 0) return cllm_memset(dst->data, 0, dst->nb[3] * (size_t) dst->ne[3], stream);
 
-    if (!is_quant(src0->type)) return launch_mul_mat_f(st, src0->type, tv(src0), tv(src1), tv(dst));
+    if (!is_quant(src0->type)) return launch_mul_mat_f(st, src0->type, tv(src0), tv(src1), tv(dst), 0, 0, src1->type);
     const int kind = act_kind(src0->type);
     const int64_t K = src0->ne[0];
     const size_t stride = act_row_bytes(K, kind);

@@ -786,7 +786,7 @@ int launch_mmvq(hipStream_t st, int wtype, const tview & w, const void * act, si
                 const tview & src1_geom, const tview & dst);
 int launch_mmvq_id(hipStream_t st, int wtype, const tview & as, const void * act, size_t act_stride, int64_t b_ne1, const tview & ids, const tview & dst);
 int launch_mmq(hipStream_t st, int wtype, const tview & w, const void * act, size_t act_stride, const tview & src1_geom, const tview & dst, const float * resid = nullptr, int64_t ldr = 0, int epi = 0);
-int launch_mul_mat_f(hipStream_t st, int wtype, const tview & w, const tview & x, const tview & d, int causal = 0, int n_past = 0);   // causal: mma_f16.hip
+int launch_mul_mat_f(hipStream_t st, int wtype, const tview & w, const tview & x, const tview & d, int causal = 0, int n_past = 0, int xtype = CLLM_TYPE_F32);   // causal: mma_f16.hip; xtype F16: with an F16 src0 only
 int launch_mma_f16(hipStream_t st, const tview & w, const tview & x, const tview & d, int causal, int n_past);
 int device_cu_count();
 // "done once PER DEVICE" flags (a bit per device id): hipFuncSetAttribute applies to the current device's copy of a kernel, and a host with several devices in one

@@ -44,6 +44,12 @@ template <> struct ld8<float> {
 // Four src1 columns share every src0 load.  (The many-column prefill contractions run on the matrix cores, mma_f16.hip: tolerance tier.)
 #include "attn_token.h"        // vd32_reduce: the tree the attention kernels take too
 
+// a src1 element at byte p as the reference's dot product sees it: an F32 src1 is rounded to src0's vec_dot_type (ld8<T>::cvt), an F16 src1 IS that type already and is
+// read in place and widened (ggml-cpu.c:1170: no converted copy)
+template <typename T, typename X> struct ldx;
+template <typename T> struct ldx<T, float>    { static __device__ __forceinline__ float at(const char * p) { return ld8<T>::cvt(*(const float *) p); } };
+template <typename T> struct ldx<T, uint16_t> { static __device__ __forceinline__ float at(const char * p) { return h2f(*(const uint16_t *) p); } };
+
 struct mmf_cols { const char * xc[4]; float * dc[4]; bool ok[4]; };
 __device__ __forceinline__ void mmf_columns(const tview & x, const tview & d, int64_t c0, int64_t ncol, int64_t i02, int64_t i03, int64_t r2, int64_t r3, mmf_cols & C) {
 #pragma unroll
@@ -57,7 +63,7 @@ __device__ __forceinline__ void mmf_columns(const tview & x, const tview & d, in
 }
 
 // grid.x over groups of 16 src0 rows (i01), grid.y = ne02*ne03
-template <typename T>
+template <typename T, typename X>
 __global__ void __launch_bounds__(256) k_mul_mat_f_vd(tview w, tview x, tview d) {
     const int tid = threadIdx.x, c16 = tid & 15;
     const int64_t i01 = (int64_t) blockIdx.x * 16 + (tid >> 4);
@@ -76,8 +82,8 @@ __global__ void __launch_bounds__(256) k_mul_mat_f_vd(tview w, tview x, tview d)
             const float w0 = ld8<T>::one(wrow + e * sizeof(T)), w1 = ld8<T>::one(wrow + (e + 1) * sizeof(T));
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                a0[c] = __builtin_fmaf(w0, ld8<T>::cvt(*(const float *)(C.xc[c] + e * 4)), a0[c]);
-                a1[c] = __builtin_fmaf(w1, ld8<T>::cvt(*(const float *)(C.xc[c] + e * 4 + 4)), a1[c]);
+                a0[c] = __builtin_fmaf(w0, ldx<T, X>::at(C.xc[c] + e * sizeof(X)), a0[c]);
+                a1[c] = __builtin_fmaf(w1, ldx<T, X>::at(C.xc[c] + e * sizeof(X) + sizeof(X)), a1[c]);
             }
         }
 #pragma unroll
@@ -86,7 +92,7 @@ __global__ void __launch_bounds__(256) k_mul_mat_f_vd(tview w, tview x, tview d)
             if (active && c16 == 0 && C.ok[c]) {
                 if (sizeof(T) == 2) {
                     double s = (double) u;
-                    for (int64_t e = np; e < K; e++) s += (double)(ld8<T>::one(wrow + e * sizeof(T)) * ld8<T>::cvt(*(const float *)(C.xc[c] + e * 4)));
+                    for (int64_t e = np; e < K; e++) s += (double)(ld8<T>::one(wrow + e * sizeof(T)) * ldx<T, X>::at(C.xc[c] + e * sizeof(X)));
                     u = (float) s;
                 } else {
                     // `sumf += x[i]*y[i]` as gcc -O3 compiles it (determined against libggml-cpu.so): whole groups of 4 leftovers have their
@@ -102,7 +108,7 @@ __global__ void __launch_bounds__(256) k_mul_mat_f_vd(tview w, tview x, tview d)
 }
 
 // grid.x over groups of 32 src0 rows, grid.y = ne02*ne03; K % 8 == 0
-template <typename T>
+template <typename T, typename X>
 __global__ void __launch_bounds__(256) k_mul_mat_f_t8(tview w, tview x, tview d) {
     const int tid = threadIdx.x, l = tid & 7;
     const int64_t i01 = (int64_t) blockIdx.x * 32 + (tid >> 3);
@@ -119,7 +125,7 @@ __global__ void __launch_bounds__(256) k_mul_mat_f_t8(tview w, tview x, tview d)
         if (active) for (int64_t k = l; k < K; k += 8) {
             const float wv = ld8<T>::one(wrow + k * sizeof(T));
 #pragma unroll
-            for (int c = 0; c < 4; c++) acc[c] = __builtin_fmaf(wv, ld8<T>::cvt(*(const float *)(C.xc[c] + k * 4)), acc[c]);
+            for (int c = 0; c < 4; c++) acc[c] = __builtin_fmaf(wv, ldx<T, X>::at(C.xc[c] + k * sizeof(X)), acc[c]);
         }
 #pragma unroll
         for (int c = 0; c < 4; c++) {
@@ -132,22 +138,30 @@ __global__ void __launch_bounds__(256) k_mul_mat_f_t8(tview w, tview x, tview d)
     }
 }
 
-template <typename T>
+template <typename T, typename X>
 static int launch_T(hipStream_t st, const tview & w, const tview & x, const tview & d) {
     const int64_t K = w.ne[0];
     if (w.ne[2] * w.ne[3] > 65535) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_f: too many batches");
     // llamafile_sgemm takes the product when n >= 2, k % 8 == 0, m % 4 == 0 (sgemm.cpp:3691, 488, 503-517); else the vec_dot loop
     // an F32 src0 reads src1 in place, and tinyBLAS is tried only on a contiguous src1 (ggml-cpu.c:1269-1271); an F16 src0 reads its dense fp16 copy of any src1
+    // an F16 src1 on an F16 src0 is read in place too (it is the vec_dot_type already): tinyBLAS with Btype F16 only when it is contiguous (sgemm.cpp:3826-3842), else
+    // the vec_dot loop through its strides -- pinned against the reference on both sides of every condition by tests/test_conv_model.py and tests/test_gpu_matmul_f16_src1.py
     bool x_cont = true;
-    for (int64_t i = 1, next = 4 * K; i < 4; next *= x.ne[i], i++) if (x.ne[i] != 1 && x.nb[i] != next) x_cont = false;
-    const bool t8 = x.ne[1] >= 2 && K % 8 == 0 && w.ne[1] % 4 == 0 && (sizeof(T) == 2 || x_cont);
-    if (t8) hipLaunchKernelGGL((k_mul_mat_f_t8<T>), dim3((unsigned)((w.ne[1] + 31) / 32), (unsigned)(w.ne[2] * w.ne[3])), dim3(256), 0, st, w, x, d);
-    else    hipLaunchKernelGGL((k_mul_mat_f_vd<T>), dim3((unsigned)((w.ne[1] + 15) / 16), (unsigned)(w.ne[2] * w.ne[3])), dim3(256), 0, st, w, x, d);
+    for (int64_t i = 1, next = (int64_t) sizeof(X) * K; i < 4; next *= x.ne[i], i++) if (x.ne[i] != 1 && x.nb[i] != next) x_cont = false;
+    const bool t8 = x.ne[1] >= 2 && K % 8 == 0 && w.ne[1] % 4 == 0 && ((sizeof(T) == 2 && sizeof(X) == 4) || x_cont);
+    if (t8) hipLaunchKernelGGL((k_mul_mat_f_t8<T, X>), dim3((unsigned)((w.ne[1] + 31) / 32), (unsigned)(w.ne[2] * w.ne[3])), dim3(256), 0, st, w, x, d);
+    else    hipLaunchKernelGGL((k_mul_mat_f_vd<T, X>), dim3((unsigned)((w.ne[1] + 15) / 16), (unsigned)(w.ne[2] * w.ne[3])), dim3(256), 0, st, w, x, d);
     LAUNCH_CHECK();
     return CLLM_OK;
 }
 
-int launch_mul_mat_f(hipStream_t st, int wtype, const tview & w, const tview & x, const tview & d, int causal, int n_past) {
+int launch_mul_mat_f(hipStream_t st, int wtype, const tview & w, const tview & x, const tview & d, int causal, int n_past, int xtype) {
+    // an F16 src1 (the im2col operand of a convolution): the lane-group kernels at every column count and in every prefill mode -- never the tolerance tier
+    // (mma_f16.hip); mmf_exact.hip (its fp16-src1 form takes the tinyBLAS order alone and is not pinned on this operand) is the follow-up if this mat-mul ever matters
+    if (xtype == CLLM_TYPE_F16) {
+        if (wtype != CLLM_TYPE_F16) FAIL(CLLM_E_UNSUPPORTED, "mul_mat_f: an F16 src1 takes an F16 src0");
+        return launch_T<uint16_t, uint16_t>(st, w, x, d);
+    }
     // many src1 columns (prefill attention): matrix cores (mma_f16.hip); few columns (decode): the lane-group mat-vec below
     static const int mma_min_cols = opt_int(OPT_CLLM_MMA_MIN_COLS);      // (below: the exact-order kernels, so that prompts of <= 32 tokens stay bit-identical to the CPU path)
     // (the exact-order matrix-core kernel has the lane-group kernels' bits: it takes over where it is faster -- CLLM_MMF_EXACT_MIN_COLS)
@@ -158,7 +172,7 @@ int launch_mul_mat_f(hipStream_t st, int wtype, const tview & w, const tview & x
                             : launch_mmf_exact(st, w, x, d, causal, n_past);       // the reference's order on the f32 matrix cores (mmf_exact.hip)
         if (rc != CLLM_E_UNSUPPORTED) return rc;
     }
-    if (wtype == CLLM_TYPE_F16) return launch_T<uint16_t>(st, w, x, d);
-    if (wtype == CLLM_TYPE_F32) return launch_T<float>(st, w, x, d);
+    if (wtype == CLLM_TYPE_F16) return launch_T<uint16_t, float>(st, w, x, d);
+    if (wtype == CLLM_TYPE_F32) return launch_T<float, float>(st, w, x, d);
     FAIL(CLLM_E_UNSUPPORTED, "mul_mat_f: type %d", wtype);
 }

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "quant_dev.h"
 
+#include <float.h>
 #include <math.h>
 #include <mutex>
 #include <vector>
@@ -909,4 +910,165 @@ extern "C" int cllm_dequantize_row(void * stream, int type, const void * blocks,
     cllm_tensor i = { CLLM_TYPE_I32, {1, 1, 1, 1}, {4, 4, 4, 4}, zero_idx };
     cllm_tensor d = { CLLM_TYPE_F32, {k, 1, 1, 1}, {4, (size_t) k*4, (size_t) k*4, (size_t) k*4}, y };
     return cllm_op_get_rows(stream, &s, &i, &d);
+}
+
+// ================================================================================================
+// IM2COL    ggml_compute_forward_im2col_f16 / _f32, ops.cpp:6117-6283 (shape rule: ggml_im2col, ggml.c:4365-4407): the first node of ggml_conv_1d / _2d
+//   dst[(n*OH*OW + oh*OW + ow) * (IC*KH*KW) + ic*KH*KW + kh*KW + kw] = src[n, ic, oh*s1 + kh*d1 - p1, ow*s0 + kw*d0 - p0], +0 outside the image
+// Pure data movement with a KH*KW-fold expansion: the stores are the traffic.  A dst row (one output position) is cut into units of 16 bytes; a team of
+// 2^tpr_shift consecutive lanes owns a row (256 >> tpr_shift rows per workgroup) and lane q of it the units q, q + team, ...: consecutive lanes store
+// consecutive 16-byte pieces.  A row's (ow, oh, n) is split once per row (t_row_coord over dst), a unit's (ic, kh, kw) once per unit and then carried;
+// the bounds test and the gather load come from the source plane.  A row that does not start on 16 bytes, and a row's leftover tail, store element by element.
+// ================================================================================================
+struct im2col_geom {
+    int64_t IW, IH, KW, KH, RL, U, rows, ofs0, ofs1;      // RL = IC*KH*KW elements per dst row, U units per row; ofs0 / ofs1: the batch / channel stride in bytes
+    int s0, s1, p0, p1, d0, d1, is_2d, tpr_shift;
+};
+// GGML_CPU_FP32_TO_FP16 of the reference's x86 build is the portable ggml_compute_fp32_to_fp16 (ggml-impl.h:401-425): round to nearest even, and every NaN becomes sign | 0x7e00
+__device__ __forceinline__ uint16_t im2col_half(uint32_t w) {
+    if ((w & 0x7fffffffu) > 0x7f800000u) return (uint16_t)(((w >> 16) & 0x8000u) | 0x7e00u);
+    return f2h(__uint_as_float(w));
+}
+// TD: uint16_t (F16 dst) or uint32_t (F32 dst: the source word as it is).  The index inside a row is 32 bits wide (the entry declines rows of 2^31 elements or more:
+// a kernel tensor of that size per output channel does not occur); rows, offsets and addresses are 64-bit
+template <typename TD>
+__global__ void __launch_bounds__(256) k_im2col(const char * __restrict__ src, tview d, im2col_geom G) {
+    constexpr int VEC = 16 / (int) sizeof(TD);
+    const int team = 1 << G.tpr_shift, rpb = 256 >> G.tpr_shift;
+    const int lr = (int) threadIdx.x >> G.tpr_shift, q0 = (int) threadIdx.x & (team - 1);
+    typedef uint32_t IX;
+    const IX RL = (IX) G.RL, U = (IX) G.U, KW = (IX) G.KW, KH = (IX) G.KH, khkw = KH * KW;
+    for (int64_t row = (int64_t) blockIdx.x * rpb + lr; row < G.rows; row += (int64_t) gridDim.x * rpb) {
+        const tcoord c = t_row_coord(d, row);                  // dst is [RL, OW, OH, N] (2-D) or [RL, OW, N, 1] (1-D)
+        const int64_t n = G.is_2d ? c.i3 : c.i2;
+        const int64_t iw0 = c.i1 * G.s0 - G.p0, ih0 = (G.is_2d ? c.i2 : 0) * G.s1 - G.p1;
+        const char * img = src + n * G.ofs0;
+        TD * drow = (TD *) d.data + row * G.RL;
+        const bool al16 = ((uintptr_t) drow & 15) == 0;
+        for (IX q = (IX) q0; q < U; q += (IX) team) {
+            const IX j = q * VEC;
+            IX ic = j / khkw, kh = (j - ic * khkw) / KW, kw = j - ic * khkw - kh * KW;
+            const int cnt = RL - j < (IX) VEC ? (int)(RL - j) : VEC;
+            TD v[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; e++) {
+                v[e] = 0;
+                if (e < cnt) {
+                    const int64_t iiw = iw0 + (int64_t) kw * G.d0, iih = ih0 + (int64_t) kh * G.d1;
+                    if (iih >= 0 && iih < G.IH && iiw >= 0 && iiw < G.IW) {
+                        const uint32_t w = *(const uint32_t *)(img + (int64_t) ic * G.ofs1 + (iih * G.IW + iiw) * 4);
+                        if (sizeof(TD) == 2) v[e] = (TD) im2col_half(w); else v[e] = (TD) w;
+                    }
+                    if (++kw == KW) { kw = 0; if (++kh == KH) { kh = 0; ic++; } }
+                }
+            }
+            TD * dp = drow + j;
+            if (al16 && cnt == VEC) {
+                u32x4 o;
+                if (sizeof(TD) == 2) o = u32x4{ (uint32_t) v[0] | (uint32_t) v[1] << 16, (uint32_t) v[2] | (uint32_t) v[3] << 16, (uint32_t) v[4 % VEC] | (uint32_t) v[5 % VEC] << 16, (uint32_t) v[6 % VEC] | (uint32_t) v[7 % VEC] << 16 };
+                else                 o = u32x4{ (uint32_t) v[0], (uint32_t) v[1], (uint32_t) v[2], (uint32_t) v[3] };
+                *(u32x4 *) dp = o;
+            } else {
+#pragma unroll
+                for (int e = 0; e < VEC; e++) if (e < cnt) dp[e] = v[e];
+            }
+        }
+    }
+}
+static int64_t conv_out_size(int64_t ins, int64_t ks, int s, int p, int d) { return (ins + 2 * (int64_t) p - (int64_t) d * (ks - 1) - 1) / s + 1; }      // ggml_calc_conv_output_size
+extern "C" int cllm_op_im2col(void * stream, const cllm_tensor * kernel, const cllm_tensor * src, cllm_tensor * dst, int s0, int s1, int p0, int p1, int d0, int d1, int is_2d) {
+    if (!kernel || !src || !dst) FAIL(CLLM_E_INVALID, "im2col: null");
+    if (src->type != CLLM_TYPE_F32 || (dst->type != CLLM_TYPE_F16 && dst->type != CLLM_TYPE_F32)) FAIL(CLLM_E_UNSUPPORTED, "im2col: type (F32 -> F16 | F32)");
+    if (dst->type == CLLM_TYPE_F16 && kernel->type != CLLM_TYPE_F16) FAIL(CLLM_E_UNSUPPORTED, "im2col: type (an F16 dst takes an F16 kernel)");       // the reference's assert, ops.cpp:6200
+    if (is_2d != 0 && is_2d != 1) FAIL(CLLM_E_INVALID, "im2col: is_2d");
+    if (s0 <= 0 || d0 <= 0 || p0 < 0 || p1 < 0 || (is_2d && (s1 <= 0 || d1 <= 0))) FAIL(CLLM_E_INVALID, "im2col: stride, padding or dilation");
+    if (src->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "im2col: rows must be dense");
+    const int64_t IW = src->ne[0], IH = is_2d ? src->ne[1] : 1, IC = is_2d ? src->ne[2] : src->ne[1], N = is_2d ? src->ne[3] : src->ne[2];
+    const int64_t KW = kernel->ne[0], KH = is_2d ? kernel->ne[1] : 1;
+    if (is_2d ? kernel->ne[2] != src->ne[2] : (kernel->ne[1] != src->ne[1] || src->ne[3] != 1)) FAIL(CLLM_E_INVALID, "im2col: shape (kernel against src)");
+    if (IW <= 0 || IH <= 0 || KW <= 0 || KH <= 0) FAIL(CLLM_E_INVALID, "im2col: shape");
+    const int64_t OW = conv_out_size(IW, KW, s0, p0, d0), OH = is_2d ? conv_out_size(IH, KH, s1, p1, d1) : 1, RL = IC * KH * KW;
+    if (OW <= 0 || OH <= 0) FAIL(CLLM_E_INVALID, "im2col: shape (src too small for the kernel)");
+    if (dst->ne[0] != RL || dst->ne[1] != OW || dst->ne[2] != (is_2d ? OH : N) || dst->ne[3] != (is_2d ? N : 1)) FAIL(CLLM_E_INVALID, "im2col: shape (dst)");
+    if (!t_is_contiguous(dst)) FAIL(CLLM_E_UNSUPPORTED, "im2col: dst must be contiguous");
+    // the reference indexes a plane as iih*IW + iiw and keeps the channel and batch strides in an int (ops.cpp:6151-6152)
+    if (is_2d && IH > 1 && src->nb[1] != (size_t) IW * 4) FAIL(CLLM_E_UNSUPPORTED, "im2col: the rows of a plane must be dense");
+    const size_t ofs0 = is_2d ? src->nb[3] : src->nb[2], ofs1 = is_2d ? src->nb[2] : src->nb[1];
+    if (ofs0 > 0x7fffffff || ofs1 > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "im2col: channel and batch strides beyond 2^31 - 1");
+    if (((uintptr_t) src->data | ofs0 | ofs1) % 4 || (uintptr_t) dst->data % cllm_type_size(dst->type)) FAIL(CLLM_E_UNSUPPORTED, "im2col: alignment");
+    if (RL > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "im2col: rows of 2^31 elements or more");
+    const int64_t rows = OW * OH * N;
+    if (rows == 0 || RL == 0) return CLLM_OK;
+    const int vec = 16 / (int) cllm_type_size(dst->type);
+    im2col_geom G = { IW, IH, KW, KH, RL, (RL + vec - 1) / vec, rows, (int64_t) ofs0, (int64_t) ofs1, s0, is_2d ? s1 : 0, p0, is_2d ? p1 : 0, d0, is_2d ? d1 : 0, is_2d, 0 };
+    while (G.tpr_shift < 8 && ((int64_t) 1 << G.tpr_shift) < G.U) G.tpr_shift++;
+    const dim3 grid(grid_1d(rows << G.tpr_shift, 16384));      // a team of 2^tpr_shift threads per row: 256 >> tpr_shift rows per workgroup
+    hipStream_t st = (hipStream_t) stream;
+    const char * sp = (const char *) src->data;
+    if (dst->type == CLLM_TYPE_F16) hipLaunchKernelGGL((k_im2col<uint16_t>), grid, dim3(256), 0, st, sp, tv(dst), G);
+    else                            hipLaunchKernelGGL((k_im2col<uint32_t>), grid, dim3(256), 0, st, sp, tv(dst), G);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// ================================================================================================
+// POOL_1D / POOL_2D    ggml_compute_forward_pool_1d_ksp / _pool_2d, ops.cpp:7182-7352 (shape rules: ggml_pool_1d / _2d, ggml.c:4848-4911): avg_pool_1d / _2d of the
+// audio and vision towers.  One thread per output element walks its window serially in the reference's order (ky outer, kx inner), skipping what lies outside the plane.
+//   AVG: a float sum from 0.0f; the 1-D form divides by the number of positions inside (none: 0.0f), the 2-D form by (float)(k0*k1) always; IEEE division
+//   MAX: from -FLT_MAX, std::max(v, res) = (v < res) ? res : v -- a NaN stays only while nothing follows it; a window of -inf alone, or wholly in the padding: -FLT_MAX
+// The 1-D form is the 2-D one over planes of one row (k1 = s1 = 1, p1 = 0) with the other divisor.
+// ================================================================================================
+struct pool_geom { int64_t IW, IH, OW, OH, planes; int op, k0, k1, s0, s1, p0, p1, by_count; };
+__global__ void __launch_bounds__(256) k_pool(const float * __restrict__ src, float * __restrict__ dst, pool_geom G) {
+    const int64_t n = G.OW * G.OH * G.planes;
+    for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
+        const int64_t ox = e % G.OW, oy = (e / G.OW) % G.OH, pl = e / (G.OW * G.OH);
+        const float * plane = src + pl * G.IH * G.IW;
+        const int64_t ix = ox * G.s0 - G.p0, iy = oy * G.s1 - G.p1;
+        float res = G.op == CLLM_POOL_AVG ? 0.0f : -FLT_MAX;
+        int count = 0;
+        for (int ky = 0; ky < G.k1; ky++) {
+            if (iy + ky < 0 || iy + ky >= G.IH) continue;
+            const float * srow = plane + (iy + ky) * G.IW;
+            for (int kx = 0; kx < G.k0; kx++) {
+                const int64_t j = ix + kx;
+                if (j < 0 || j >= G.IW) continue;
+                const float v = srow[j];
+                if (G.op == CLLM_POOL_AVG) res = res + v; else res = (v < res) ? res : v;
+                count++;
+            }
+        }
+        if (G.op == CLLM_POOL_AVG) {
+            if (G.by_count) res = count > 0 ? __fdiv_rn(res, (float) count) : 0.0f;
+            else            res = __fdiv_rn(res, (float)(G.k0 * G.k1));
+        }
+        dst[e] = res;
+    }
+}
+// ggml_calc_pool_output_size: (ins + 2*p - ks) / s + 1 in float (p is a float there), truncated
+static int64_t pool_out_size(int64_t ins, int ks, int s, int p) { return (int64_t)(((float) ins + 2.0f * (float) p - (float) ks) / (float) s + 1.0f); }
+static int pool_launch(void * stream, const char * name, int op, const cllm_tensor * src, cllm_tensor * dst, int k0, int k1, int s0, int s1, int p0, int p1, bool is_2d) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "%s: null", name);
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "%s: type (F32 only)", name);
+    if (op != CLLM_POOL_MAX && op != CLLM_POOL_AVG) FAIL(CLLM_E_INVALID, "%s: op %d", name, op);
+    if (k0 <= 0 || k1 <= 0 || s0 <= 0 || s1 <= 0 || p0 < 0 || p1 < 0) FAIL(CLLM_E_INVALID, "%s: kernel, stride or padding", name);
+    if (!t_is_contiguous(src) || !t_is_contiguous(dst)) FAIL(CLLM_E_UNSUPPORTED, "%s: src and dst must be contiguous", name);
+    const int64_t IW = src->ne[0], IH = is_2d ? src->ne[1] : 1;
+    // the reference walks a window in int (ops.cpp:7217, 7316-7317) and multiplies k0 * k1 in int
+    if (IW + 2 * (int64_t) p0 + k0 > 0x7fffffff || IH + 2 * (int64_t) p1 + k1 > 0x7fffffff || (int64_t) k0 * k1 > 0x7fffffff) FAIL(CLLM_E_UNSUPPORTED, "%s: extent beyond 2^31 - 1", name);
+    const int64_t OW = IW > 0 ? pool_out_size(IW, k0, s0, p0) : 0, OH = is_2d ? (IH > 0 ? pool_out_size(IH, k1, s1, p1) : 0) : 1;
+    const bool empty = t_nelements(src) == 0;
+    if (!empty && (OW <= 0 || OH <= 0)) FAIL(CLLM_E_INVALID, "%s: shape (src too small for the window)", name);
+    if (dst->ne[0] != OW || dst->ne[1] != (is_2d ? OH : src->ne[1]) || dst->ne[2] != src->ne[2] || dst->ne[3] != src->ne[3]) FAIL(CLLM_E_INVALID, "%s: shape", name);
+    if (empty || t_nelements(dst) == 0) return CLLM_OK;
+    pool_geom G = { IW, IH, OW, OH, is_2d ? src->ne[2] * src->ne[3] : t_nrows(src), op, k0, k1, s0, s1, p0, p1, is_2d ? 0 : 1 };
+    hipLaunchKernelGGL(k_pool, dim3(grid_1d(t_nelements(dst), 8192)), dim3(256), 0, (hipStream_t) stream, (const float *) src->data, (float *) dst->data, G);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+extern "C" int cllm_op_pool_1d(void * stream, int op, const cllm_tensor * src, cllm_tensor * dst, int k0, int s0, int p0) {
+    return pool_launch(stream, "pool_1d", op, src, dst, k0, 1, s0, 1, p0, 0, false);
+}
+extern "C" int cllm_op_pool_2d(void * stream, int op, const cllm_tensor * src, cllm_tensor * dst, int k0, int k1, int s0, int s1, int p0, int p1) {
+    return pool_launch(stream, "pool_2d", op, src, dst, k0, k1, s0, s1, p0, p1, true);
 }

@@ -374,6 +374,10 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
     switch (op->op) {
         case GGML_OP_NONE: case GGML_OP_RESHAPE: case GGML_OP_VIEW: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE: return true;
         case GGML_OP_MUL_MAT:
+            // an F16 b with an F16 a (the IM2COL operand of ggml_conv_1d / _2d): check_mm's predicates for it -- dense halves, strides that are multiples of 2
+            if (b && b->type == GGML_TYPE_F16)
+                return a->type == GGML_TYPE_F16 && op->type == GGML_TYPE_F32 && dense_rows(a) && b->nb[0] == 2 && b->nb[1] % 2 == 0 && b->nb[2] % 2 == 0 && b->nb[3] % 2 == 0 &&
+                       a->ne[2] * a->ne[3] <= 65535;
             if (!f32_dense(b) || op->type != GGML_TYPE_F32 || !dense_rows(a)) return false;
             // (the predicates of cllm_op_mul_mat / check_mm that do not depend on the data pointers: what is declined here runs on the CPU backend
             // instead of failing in graph_compute; buffers of this module are 256-byte aligned and ggml-alloc keeps that alignment)
@@ -444,6 +448,28 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
             const bool fs = s == GGML_TYPE_F32 || s == GGML_TYPE_F16, fd = d == GGML_TYPE_F32 || d == GGML_TYPE_F16;
             if (s == d && is_q(s)) return a->ne[0] == op->ne[0] && a->nb[0] == ggml_type_size(s) && op->nb[0] == ggml_type_size(s);      // whole quantized rows (CONT of the Q8_0 K-cache view)
             return (fs && fd) || (s == GGML_TYPE_I32 && d == GGML_TYPE_I32);
+        }
+        case GGML_OP_IM2COL: {     // cllm_op_im2col's own predicates (a: the kernel, read for its shape and type; b: the image); dst ne is ggml_im2col's by construction
+            const int32_t * q = op->op_params;      // s0, s1, p0, p1, d0, d1, is_2D
+            const bool two = q[6] == 1;
+            if (q[6] != 0 && q[6] != 1) return false;
+            if (!a || !f32_dense(b) || (op->type != GGML_TYPE_F16 && op->type != GGML_TYPE_F32) || (op->type == GGML_TYPE_F16 && a->type != GGML_TYPE_F16) || !ggml_is_contiguous(op)) return false;
+            if (q[0] <= 0 || q[4] <= 0 || q[2] < 0 || q[3] < 0 || (two && (q[1] <= 0 || q[5] <= 0))) return false;
+            if (two ? a->ne[2] != b->ne[2] : (a->ne[1] != b->ne[1] || b->ne[3] != 1)) return false;
+            if (two && b->ne[1] > 1 && b->nb[1] != (size_t) b->ne[0] * 4) return false;
+            const size_t ofs0 = two ? b->nb[3] : b->nb[2], ofs1 = two ? b->nb[2] : b->nb[1];
+            return ofs0 <= 0x7fffffff && ofs1 <= 0x7fffffff && ofs0 % 4 == 0 && ofs1 % 4 == 0 && op->ne[0] <= 0x7fffffff;
+        }
+        case GGML_OP_POOL_1D: case GGML_OP_POOL_2D: {      // cllm_op_pool_1d / _2d's: F32 and contiguous on both sides, op MAX | AVG, k, s > 0, p >= 0 (dst ne is the constructor's)
+            const int32_t * q = op->op_params;      // 1-D: op, k0, s0, p0; 2-D: op, k0, k1, s0, s1, p0, p1
+            if (!a || a->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_is_contiguous(a) || !ggml_is_contiguous(op) || (q[0] != GGML_OP_POOL_MAX && q[0] != GGML_OP_POOL_AVG)) return false;
+            // the entries recompute dst ne from the int parameters (ggml_calc_pool_output_size, in float as there); ggml_pool_2d computes it from its float paddings and
+            // stores them truncated, so a fractional padding may give another ne: such a node stays on the CPU backend
+            auto out = [](int64_t ins, int ks, int s, int p) { return (int64_t)(((float) ins + 2.0f * (float) p - (float) ks) / (float) s + 1.0f); };
+            if (op->op == GGML_OP_POOL_1D) return q[1] > 0 && q[2] > 0 && q[3] >= 0 && a->ne[0] + 2 * (int64_t) q[3] + q[1] <= 0x7fffffff && op->ne[0] == out(a->ne[0], q[1], q[2], q[3]);
+            return q[1] > 0 && q[2] > 0 && q[3] > 0 && q[4] > 0 && q[5] >= 0 && q[6] >= 0 && (int64_t) q[1] * q[2] <= 0x7fffffff &&
+                   a->ne[0] + 2 * (int64_t) q[5] + q[1] <= 0x7fffffff && a->ne[1] + 2 * (int64_t) q[6] + q[2] <= 0x7fffffff &&
+                   op->ne[0] == out(a->ne[0], q[1], q[3], q[5]) && op->ne[1] == out(a->ne[1], q[2], q[4], q[6]);
         }
         case GGML_OP_GET_ROWS: return (is_q(a->type) || is_kq(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) && b->type == GGML_TYPE_I32 && op->type == GGML_TYPE_F32;
         default: return false;
@@ -1006,6 +1032,9 @@ ggml_status walk(walk_ctx & w, fuse_plan & plan, sig_writer * sw) {
             case GGML_OP_FLASH_ATTN_EXT: rc = issue_flash_attn_ext(w, io); break;
             case GGML_OP_CPY: case GGML_OP_DUP: case GGML_OP_CONT: rc = plan.attn[i] >= 0 ? issue_attention(w, plan, i) : E(cllm_op_cpy, st, &da, &d); break;
             case GGML_OP_GET_ROWS:       rc = E(cllm_op_get_rows, st, &da, &db, &d); break;
+            case GGML_OP_IM2COL:         { const int32_t * q = n->op_params; rc = E(cllm_op_im2col, st, &da, &db, &d, (int) q[0], (int) q[1], (int) q[2], (int) q[3], (int) q[4], (int) q[5], (int) q[6]); } break;
+            case GGML_OP_POOL_1D:        { const int32_t * q = n->op_params; rc = E(cllm_op_pool_1d, st, (int) q[0], &da, &d, (int) q[1], (int) q[2], (int) q[3]); } break;      // cllm_pool == ggml_op_pool
+            case GGML_OP_POOL_2D:        { const int32_t * q = n->op_params; rc = E(cllm_op_pool_2d, st, (int) q[0], &da, &d, (int) q[1], (int) q[2], (int) q[3], (int) q[4], (int) q[5], (int) q[6]); } break;
             default: HIPB_LOG("graph_compute: op %s reached the device although supports_op() declined it", ggml_op_name(n->op)); return GGML_STATUS_FAILED;
         }
         if (rc != CLLM_OK) {

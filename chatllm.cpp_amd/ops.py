@@ -320,5 +320,62 @@ def get_rows(a, idx, dst=None):
     return dst
 
 
+POOL_MAX, POOL_AVG = 0, 1      # == enum ggml_op_pool
+
+
+def _conv_out(ins, ks, s, p, d):
+    """ggml_calc_conv_output_size (C division: it truncates toward zero)"""
+    num = ins + 2 * p - d * (ks - 1) - 1
+    return (num // s if num >= 0 else -(-num // s)) + 1
+
+
+def _pool_out(ins, ks, s, p):
+    """ggml_calc_pool_output_size (a float expression there; the same for the integer paddings this interface takes)"""
+    return (ins + 2 * p - ks) // s + 1 if ins + 2 * p >= ks else 0
+
+
+def im2col(kernel, src, s0, s1, p0, p1, d0, d1, is_2d, dst_type=F16, dst=None):
+    """ggml_im2col(kernel, src, ...): [N, IC, IH, IW] -> [N, OH, OW, IC*KH*KW]; the kernel is read for its shape and type only"""
+    if dst is None:
+        ow = _conv_out(src.ne[0], kernel.ne[0], s0, p0, d0)
+        if is_2d:
+            ne = [kernel.ne[2] * kernel.ne[1] * kernel.ne[0], ow, _conv_out(src.ne[1], kernel.ne[1], s1, p1, d1), src.ne[3]]
+        else:
+            ne = [kernel.ne[1] * kernel.ne[0], ow, src.ne[2], 1]
+        dst = Tensor(dst_type, ne)
+    _l.check(_l.get().cllm_op_im2col(None, _ref(kernel), _ref(src), _ref(dst), s0, s1, p0, p1, d0, d1, 1 if is_2d else 0), "im2col")
+    return dst
+
+
+def pool_1d(a, op, k0, s0, p0, dst=None):
+    """ggml::avg_pool_1d and its MAX form (ggml_pool_1d): [IW, ...] -> [OW, ...]"""
+    dst = dst or Tensor(F32, [_pool_out(a.ne[0], k0, s0, p0), a.ne[1], a.ne[2], a.ne[3]])
+    _l.check(_l.get().cllm_op_pool_1d(None, op, _ref(a), _ref(dst), k0, s0, p0), "pool_1d")
+    return dst
+
+
+def pool_2d(a, op, k0, k1, s0, s1, p0, p1, dst=None):
+    """ggml::avg_pool_2d and its MAX form (ggml_pool_2d): [IW, IH, ...] -> [OW, OH, ...]"""
+    dst = dst or Tensor(F32, [_pool_out(a.ne[0], k0, s0, p0), _pool_out(a.ne[1], k1, s1, p1), a.ne[2], a.ne[3]])
+    _l.check(_l.get().cllm_op_pool_2d(None, op, _ref(a), _ref(dst), k0, k1, s0, s1, p0, p1), "pool_2d")
+    return dst
+
+
+def conv_1d(kernel, data, stride, padding, dilation):
+    """ggml::conv_1d (src/layers.cpp:1378; ggml_conv_1d, ggml.c:4434-4451), node by node: IM2COL to F16, MUL_MAT of the reshaped im2col (src0) and kernel (src1),
+    RESHAPE to [OL, OC, N].  kernel [K, IC, OC] F16, data [IW, IC, N] F32"""
+    col = im2col(kernel, data, stride, 0, padding, 0, dilation, 0, False, F16)
+    out = mul_mat(col.reshape(col.ne[0], col.ne[2] * col.ne[1]), kernel.reshape(kernel.ne[0] * kernel.ne[1], kernel.ne[2]))
+    return out.reshape(col.ne[1], kernel.ne[2], col.ne[2])
+
+
+def conv_2d(kernel, data, s0, s1, p0, p1, d0, d1):
+    """ggml::conv_2d (src/layers.cpp:1362; ggml_conv_2d, ggml.c:4536-4558), node by node: IM2COL to the kernel's type, MUL_MAT of the reshaped im2col (src0) and
+    kernel (src1), RESHAPE to [OW, OH, N, OC], PERMUTE(0, 1, 3, 2), CONT -> [OW, OH, OC, N].  kernel [KW, KH, IC, OC] F16 | F32, data [IW, IH, IC, N] F32"""
+    col = im2col(kernel, data, s0, s1, p0, p1, d0, d1, True, kernel.type)
+    out = mul_mat(col.reshape(col.ne[0], col.ne[3] * col.ne[2] * col.ne[1]), kernel.reshape(kernel.ne[0] * kernel.ne[1] * kernel.ne[2], kernel.ne[3]))
+    return cont(out.reshape(col.ne[1], col.ne[2], col.ne[3], kernel.ne[3]).permute(0, 1, 3, 2))
+
+
 def sync():
     _l.check(_l.get().cllm_stream_sync(None), "sync")

@@ -119,6 +119,9 @@ CLLM_API int  cllm_memcpy_peer_async(void * dst, int dst_device, const void * sr
  * type's vec_dot_type (Q8_0: id=127/amax, round-half-even, arch/x86/quants.c:290-345;  Q8_1 for Q4_1: the
  * same plus s = fp16(d*sum q), :388-480;  Q8_K: ggml-quants.c:2555-2592;  F16: RNE), block dot products are
  * exact int32, scaling/accumulation fp32.
+ * src1 may be F16 when src0 is F16 (the mat-mul of ggml_conv_1d / _2d: im2col x kernel): it is src0's vec_dot_type already and is read in place, as the
+ * reference reads it (ggml-cpu.c:1170-1210) -- tinyBLAS order when it is contiguous (and ne11 >= 2, K % 8 == 0, ne01 % 4 == 0), ggml_vec_dot_f16 through its strides
+ * otherwise; bit-identical at any column count and in every prefill mode.  nb[0] == 2, data and strides multiples of 2; with any other src0: CLLM_E_UNSUPPORTED.
  * `wdata` is scratch for the converted src1 (ggml's params->wdata): at least cllm_mul_mat_wsize() bytes.
  */
 CLLM_API size_t cllm_mul_mat_wsize(const cllm_tensor * src0, const cllm_tensor * src1);
@@ -368,6 +371,26 @@ CLLM_API int cllm_op_set_rows(void * stream, const cllm_tensor * src, const cllm
 CLLM_API int cllm_op_cpy(void * stream, const cllm_tensor * src, cllm_tensor * dst);
 /* GGML_OP_GET_ROWS      ggml_compute_forward_get_rows (ops.cpp:4653-4700,4820): embedding gather with dequantization */
 CLLM_API int cllm_op_get_rows(void * stream, const cllm_tensor * src, const cllm_tensor * idx, cllm_tensor * dst);
+/* GGML_OP_IM2COL        ggml_compute_forward_im2col_f16 / _f32 (ggml-cpu/ops.cpp:6117-6283; shape rule ggml_im2col, ggml.c:4365-4407): the first node of ggml_conv_1d / _1d_dw /
+ * _2d / _2d_dw (ggml.c:4434-4700; Conv1D::forward, Conv2D::forward, src/layers.cpp:1864-1928).  `kernel` is read for its shape and type only (its data may be NULL).
+ *   dst[(n*OH*OW + oh*OW + ow) * (IC*KH*KW) + ic*KH*KW + kh*KW + kw] = src[n, ic, oh*s1 + kh*d1 - p1, ow*s0 + kw*d0 - p0], +0 where that lies outside the image;
+ *   1-D (is_2d == 0): KH = OH = IH = 1, src [IW, IC, N, 1], kernel [KW, IC, ..], dst [IC*KW, OW, N, 1]; 2-D: src [IW, IH, IC, N], kernel [KW, KH, IC, ..], dst [IC*KH*KW, OW, OH, N].
+ * src F32 with nb[0] == 4, in 2-D nb[1] == IW*4 (the reference indexes a plane densely); the channel and batch strides are honoured and must fit an int, as there.
+ * dst contiguous: F32 (the source word as it is) or F16 (GGML_CPU_FP32_TO_FP16 of the x86 build: round to nearest even, every NaN becomes sign | 0x7e00; needs an F16 kernel).
+ * s0, d0 > 0 (2-D: s1, d1 > 0), p0, p1 >= 0; dst ne by ggml_im2col's rule; 1-D: kernel->ne[1] == src->ne[1], src->ne[3] == 1; 2-D: kernel->ne[2] == src->ne[2].
+ * CLLM_E_UNSUPPORTED: types, strides, dst rows of 2^31 elements or more; CLLM_E_INVALID: null, shapes, parameters.  An empty tensor: CLLM_OK, no launch.  A declined call leaves dst untouched. */
+CLLM_API int cllm_op_im2col(void * stream, const cllm_tensor * kernel, const cllm_tensor * src, cllm_tensor * dst, int s0, int s1, int p0, int p1, int d0, int d1, int is_2d);
+/* numeric values == enum ggml_op_pool (ggml.h) */
+typedef enum cllm_pool { CLLM_POOL_MAX = 0, CLLM_POOL_AVG = 1 } cllm_pool;
+/* GGML_OP_POOL_1D       ggml_compute_forward_pool_1d (ggml-cpu/ops.cpp:7182-7265; shape rule ggml_pool_1d, ggml.c:4848-4878): dst [OW, ne1, ne2, ne3], each window walked serially.
+ * GGML_OP_POOL_2D       ggml_compute_forward_pool_2d (ggml-cpu/ops.cpp:7269-7352; shape rule ggml_pool_2d, ggml.c:4882-4911): dst [OW, OH, ne2, ne3], ky outer, kx inner.
+ * (ggml::avg_pool_1d / avg_pool_2d of the audio and vision towers.)  Positions outside the plane are skipped.  AVG: a float sum from 0.0f; the 1-D form divides by the
+ * number of positions inside (none: 0.0f), the 2-D form by (float)(k0*k1) always.  MAX: from -FLT_MAX with (v < res) ? res : v: a NaN stays only while nothing follows it in
+ * the window; a window of -inf alone or wholly in the padding gives -FLT_MAX.  Every word has the bits of the reference's CPU build.  F32 and contiguous on both sides,
+ * k, s > 0, p >= 0, dst ne by the reference's rule.  CLLM_E_UNSUPPORTED: another type (an F16 source too), views; CLLM_E_INVALID: null, shapes, parameters, another op.
+ * An empty tensor: CLLM_OK, no launch.  A declined call leaves dst untouched. */
+CLLM_API int cllm_op_pool_1d(void * stream, int op /* cllm_pool */, const cllm_tensor * src, cllm_tensor * dst, int k0, int s0, int p0);
+CLLM_API int cllm_op_pool_2d(void * stream, int op /* cllm_pool */, const cllm_tensor * src, cllm_tensor * dst, int k0, int k1, int s0, int s1, int p0, int p1);
 /* WEIGHT quantizers on the device: quantize_row_{q8_0,q4_0,q4_1,q5_0,q5_1,q4_K}_ref and the F16 conversion (ggml/src/ggml-quants.c:36-222, 622-702, 1280-1350),
  * byte-identical to the reference's from_float_ref.  Replaces the host-side loop of ggml::from_float (src/layers.cpp:358-373) that chatllm.cpp's loader runs when a
  * tensor is re-quantized on load (src/chat.cpp:1246-1279): nrows rows of k fp32 values at x (device, contiguous, 16-byte aligned) -> rows of `type` blocks at y. */
