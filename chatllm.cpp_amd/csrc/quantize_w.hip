@@ -13,6 +13,13 @@
 #include "quant_dev.h"
 #include "q4k.h"
 
+// (int8_t) f and (uint8_t) f as the reference build converts them: cvttss2si to int32, the low byte kept.  C leaves the conversion undefined where the truncated
+// value does not fit, and that is reached: id = 1 / d is inf for |d| < 2^-128 (a Q8_0 block maximum below 3.73e-37, a Q4_0 / Q5_0 one below 2.35e-38 / 4.70e-38,
+// a Q4_1 / Q5_1 range below 4.41e-38 / 9.11e-38), the products are +-inf and, for the block's zeros, NaN.  cvttss2si answers 0x80000000 for those, low byte 0:
+// every quant of such a block is 0.  v_cvt_i32_f32 saturates instead (+inf -> INT_MAX: 0xff, nibble 15, 31), so the range is tested here
+// (tests/test_weight_quant_model.py states the reference's bytes, tests/test_gpu_weight_quant.py these)
+__device__ __forceinline__ int cvtt_low_byte(float f) { return fabsf(f) < 0x1p31f ? (int) f & 0xff : 0; }      // false for NaN
+
 template <int TYPE>
 __global__ void __launch_bounds__(256) k_quantize_b32(const float * __restrict__ x, char * __restrict__ y, int64_t nblocks) {
     const int64_t b = (int64_t) blockIdx.x * 256 + threadIdx.x;
@@ -43,7 +50,7 @@ __global__ void __launch_bounds__(256) k_quantize_b32(const float * __restrict__
     if (!SIGNED) { const uint16_t mh = f2h(mn); out[2] = (uint8_t)(mh & 0xff); out[3] = (uint8_t)(mh >> 8); o = 4; }
     if (TYPE == CLLM_TYPE_Q8_0) {
 #pragma unroll
-        for (int j = 0; j < 32; j++) out[2 + j] = (uint8_t)(int8_t) roundf(v[j] * id);          // roundf: halves away from zero (ggml-quants.c:199-222)
+        for (int j = 0; j < 32; j++) out[2 + j] = (uint8_t) cvtt_low_byte(roundf(v[j] * id));   // roundf: halves away from zero (ggml-quants.c:199-222)
     } else {
         constexpr bool Q5 = TYPE == CLLM_TYPE_Q5_0 || TYPE == CLLM_TYPE_Q5_1;
         constexpr int QMAX = Q5 ? 31 : 15;
@@ -53,8 +60,8 @@ __global__ void __launch_bounds__(256) k_quantize_b32(const float * __restrict__
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const float x0 = SIGNED ? v[j] * id : (v[j] - mn) * id, x1 = SIGNED ? v[j + 16] * id : (v[j + 16] - mn) * id;
-            int q0 = (int)(x0 + off), q1 = (int)(x1 + off);                                      // (int8_t) of a value in 0 .. 32: the truncation
-            if (TYPE != CLLM_TYPE_Q5_1) { q0 = q0 < QMAX ? q0 : QMAX; q1 = q1 < QMAX ? q1 : QMAX; }   // (Q5_1 does not clamp: (uint8_t)(x + 0.5f) <= 31)
+            int q0 = cvtt_low_byte(x0 + off), q1 = cvtt_low_byte(x1 + off);                      // (int8_t) / (uint8_t) of a value in 0 .. 32: the truncation
+            if (TYPE != CLLM_TYPE_Q5_1) { q0 = (int8_t) q0; q1 = (int8_t) q1; q0 = q0 < QMAX ? q0 : QMAX; q1 = q1 < QMAX ? q1 : QMAX; }   // MIN(QMAX, (int8_t) .); (Q5_1 does not clamp: (uint8_t)(x + 0.5f) <= 31)
             out[qo + j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
             if (Q5) { qh |= (uint32_t)((q0 >> 4) & 1) << j; qh |= (uint32_t)((q1 >> 4) & 1) << (j + 16); }
         }

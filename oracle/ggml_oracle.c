@@ -137,6 +137,14 @@ void orc_quantize_row_q8_1(const float * x, orc_block_q8_1 * y, int64_t k) {
     }
 }
 
+/* (int8_t) f and (uint8_t) f as the reference build converts them (x86-64: cvttss2si / cvttps2dq to int32, the low byte kept).  C leaves the conversion undefined
+ * where the truncated value does not fit, and that is reached: a block whose scale d is below 2^-128 in magnitude has id = 1 / d = inf, its products are +-inf
+ * and, for the block's zeros, NaN.  The instruction answers 0x80000000 for NaN and for everything outside int32, whose low byte is 0: every quant of such a
+ * block is 0 (tests/test_weight_quant_model.py states this from the reference alone).  Written out so that it does not depend on this file's compiler */
+static inline int32_t cvtt_i32(float f) { return fabsf(f) < 0x1p31f ? (int32_t) f : INT32_MIN; }      /* false for NaN */
+static inline int8_t  cast_i8(float f)  { return (int8_t)(uint8_t)((uint32_t) cvtt_i32(f) & 0xffu); }
+static inline uint8_t cast_u8(float f)  { return (uint8_t)((uint32_t) cvtt_i32(f) & 0xffu); }
+
 /* ggml-quants.c:199-222: id = 1/d, roundf (half away from zero) */
 void orc_quantize_row_q8_0_ref(const float * x, orc_block_q8_0 * y, int64_t k) {
     const int64_t nb = k / ORC_QK;
@@ -146,7 +154,7 @@ void orc_quantize_row_q8_0_ref(const float * x, orc_block_q8_0 * y, int64_t k) {
         const float d  = amax / 127;
         const float id = d ? 1.0f/d : 0.0f;
         y[i].d = orc_fp32_to_fp16(d);
-        for (int j = 0; j < ORC_QK; j++) y[i].qs[j] = (int8_t) roundf(x[i*ORC_QK + j] * id);
+        for (int j = 0; j < ORC_QK; j++) y[i].qs[j] = cast_i8(roundf(x[i*ORC_QK + j] * id));
     }
 }
 
@@ -1119,7 +1127,7 @@ void orc_quantize_row_q4_0_ref(const float * x, orc_block_q4_0 * y, int64_t k) {
         y[i].d = orc_fp32_to_fp16(d);
         for (int j = 0; j < 16; j++) {
             const float x0 = x[j] * id, x1 = x[j + 16] * id;
-            const uint8_t q0 = (uint8_t) ORC_MIN(15, (int8_t)(x0 + 8.5f)), q1 = (uint8_t) ORC_MIN(15, (int8_t)(x1 + 8.5f));
+            const uint8_t q0 = (uint8_t) ORC_MIN(15, cast_i8(x0 + 8.5f)), q1 = (uint8_t) ORC_MIN(15, cast_i8(x1 + 8.5f));
             y[i].qs[j] = (uint8_t)(q0 | (q1 << 4));
         }
     }
@@ -1131,7 +1139,7 @@ void orc_quantize_row_q4_1_ref(const float * x, orc_block_q4_1 * y, int64_t k) {
         y[i].d = orc_fp32_to_fp16(d); y[i].m = orc_fp32_to_fp16(mn);
         for (int j = 0; j < 16; j++) {
             const float x0 = (x[j] - mn) * id, x1 = (x[j + 16] - mn) * id;
-            const uint8_t q0 = (uint8_t) ORC_MIN(15, (int8_t)(x0 + 0.5f)), q1 = (uint8_t) ORC_MIN(15, (int8_t)(x1 + 0.5f));
+            const uint8_t q0 = (uint8_t) ORC_MIN(15, cast_i8(x0 + 0.5f)), q1 = (uint8_t) ORC_MIN(15, cast_i8(x1 + 0.5f));
             y[i].qs[j] = (uint8_t)(q0 | (q1 << 4));
         }
     }
@@ -1143,7 +1151,7 @@ void orc_quantize_row_q5_0_ref(const float * x, orc_block_q5_0 * y, int64_t k) {
         uint32_t qh = 0;
         for (int j = 0; j < 16; j++) {
             const float x0 = x[j] * id, x1 = x[j + 16] * id;
-            const uint8_t q0 = (uint8_t) ORC_MIN(31, (int8_t)(x0 + 16.5f)), q1 = (uint8_t) ORC_MIN(31, (int8_t)(x1 + 16.5f));
+            const uint8_t q0 = (uint8_t) ORC_MIN(31, cast_i8(x0 + 16.5f)), q1 = (uint8_t) ORC_MIN(31, cast_i8(x1 + 16.5f));
             y[i].qs[j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
             qh |= (uint32_t)((q0 & 0x10u) >> 4) << j;
             qh |= (uint32_t)((q1 & 0x10u) >> 4) << (j + 16);
@@ -1159,7 +1167,7 @@ void orc_quantize_row_q5_1_ref(const float * x, orc_block_q5_1 * y, int64_t k) {
         uint32_t qh = 0;
         for (int j = 0; j < 16; j++) {
             const float x0 = (x[j] - mn) * id, x1 = (x[j + 16] - mn) * id;
-            const uint8_t q0 = (uint8_t)(x0 + 0.5f), q1 = (uint8_t)(x1 + 0.5f);
+            const uint8_t q0 = cast_u8(x0 + 0.5f), q1 = cast_u8(x1 + 0.5f);
             y[i].qs[j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
             qh |= (uint32_t)((q0 & 0x10u) >> 4) << j;
             qh |= (uint32_t)((q1 & 0x10u) >> 4) << (j + 16);

@@ -625,7 +625,8 @@ def test_cpy_v_cache_transposed_and_cont(gpu):
 @pytest.mark.parametrize("t", [O.Q8_0, O.Q4_0, O.Q4_1, O.Q5_0, O.Q5_1, O.Q4_K, O.F16])
 def test_weight_quantizers_on_the_device_are_byte_identical(gpu, t):
     """cllm_op_quantize_rows == the reference's from_float_ref (the loader's on-load re-quantization), byte for byte: random rows at three magnitudes plus the
-    special sub-blocks (all zero, constant, all positive, ties, values on the rounding grid); a re-quantized row then dequantizes to the same floats"""
+    special sub-blocks (all zero, constant, all positive, ties, values on the rounding grid).  One shape; the edge blocks, the launch geometries, the declines and
+    the round trip through cllm_dequantize_row are tests/test_gpu_weight_quant.py"""
     T, L = gpu.Tensor, gpu.lib.get()
     K, rows = 4096, 37
     for scale in (1.0, 1e-3, 40.0):
