@@ -1072,3 +1072,219 @@ extern "C" int cllm_op_pool_1d(void * stream, int op, const cllm_tensor * src, c
 extern "C" int cllm_op_pool_2d(void * stream, int op, const cllm_tensor * src, cllm_tensor * dst, int k0, int k1, int s0, int s1, int p0, int p1) {
     return pool_launch(stream, "pool_2d", op, src, dst, k0, k1, s0, s1, p0, p1, true);
 }
+
+// ================================================================================================
+// PAD / PAD_REFLECT_1D / UPSCALE / CONV_TRANSPOSE_1D: what the audio and vision front ends put around their convolutions (the left pad of a causal Conv1D, the
+// Conformer's chunking, Conv1D's reflect padding, ggml::interpolate, the vocoder's ConvTransposed1D).  The destination of all four is contiguous.
+// The two pads share k_im2col's store shape: a thread owns 4 consecutive words of a dst row (unit q of row r is item r * U + q of the 1-D walk, so consecutive lanes
+// store consecutive 16-byte pieces); a row that does not start on 16 bytes, and a row's leftover tail, store word by word.  Words are moved as words: NaN payloads stay.
+// ================================================================================================
+__device__ __forceinline__ void pad_store4(uint32_t * dp, bool al16, int cnt, const uint32_t (&v)[4]) {
+    if (al16 && cnt == 4) { *(u32x4 *) dp = u32x4{ v[0], v[1], v[2], v[3] }; return; }
+#pragma unroll
+    for (int e = 0; e < 4; e++) if (e < cnt) dp[e] = v[e];
+}
+// PAD       ggml_compute_forward_pad_f32<false>, ops.cpp:7696-7758 (shape rule: ggml_pad_ext, ggml.c:5016-5049): dst is addressed densely, the source through its four
+// byte strides (nb00 too); inside [lp, ne - rp) on every axis the source word, +0.0f elsewhere
+struct pad_geom { int64_t U; int lp0, lp1, lp2, lp3; };
+__global__ void __launch_bounds__(256) k_pad(tview s, tview d, pad_geom G) {
+    const int64_t n = G.U * d.ne[1] * d.ne[2] * d.ne[3];
+    for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
+        const tcoord c = t_unit_coord(G.U, d, e);
+        const int64_t j = c.i0 * 4;
+        uint32_t * drow = (uint32_t *) d.data + (e / G.U) * d.ne[0];
+        const tcoord sc = { 0, c.i1 - G.lp1, c.i2 - G.lp2, c.i3 - G.lp3 };
+        const bool inside = sc.i1 >= 0 && sc.i1 < s.ne[1] && sc.i2 >= 0 && sc.i2 < s.ne[2] && sc.i3 >= 0 && sc.i3 < s.ne[3];
+        const char * srow = t_row_at(s, inside ? sc : tcoord{ 0, 0, 0, 0 });
+        const int cnt = d.ne[0] - j < 4 ? (int)(d.ne[0] - j) : 4;
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t i00 = j + k - G.lp0;
+            v[k] = 0;
+            if (k < cnt && inside && i00 >= 0 && i00 < s.ne[0]) v[k] = *(const uint32_t *)(srow + i00 * s.nb[0]);
+        }
+        pad_store4(drow + j, ((uintptr_t) drow & 15) == 0, cnt, v);
+    }
+}
+extern "C" int cllm_op_pad(void * stream, const cllm_tensor * src, cllm_tensor * dst, int lp0, int rp0, int lp1, int rp1, int lp2, int rp2, int lp3, int rp3) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "pad: null");
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "pad: type (F32 only)");
+    const int lp[4] = { lp0, lp1, lp2, lp3 }, rp[4] = { rp0, rp1, rp2, rp3 };
+    for (int i = 0; i < 4; i++) if (lp[i] < 0 || rp[i] < 0) FAIL(CLLM_E_INVALID, "pad: negative padding");
+    for (int i = 0; i < 4; i++) if (dst->ne[i] != src->ne[i] + lp[i] + rp[i]) FAIL(CLLM_E_INVALID, "pad: shape");
+    if (!t_is_contiguous(dst)) FAIL(CLLM_E_UNSUPPORTED, "pad: dst must be contiguous");
+    if (((uintptr_t) src->data | (uintptr_t) dst->data | src->nb[0] | src->nb[1] | src->nb[2] | src->nb[3]) % 4) FAIL(CLLM_E_UNSUPPORTED, "pad: alignment");
+    if (t_nelements(dst) == 0) return CLLM_OK;
+    pad_geom G = { (dst->ne[0] + 3) / 4, lp0, lp1, lp2, lp3 };
+    hipLaunchKernelGGL(k_pad, dim3(grid_1d(G.U * t_nrows(dst), 16384)), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), G);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// PAD_REFLECT_1D    ggml_compute_forward_pad_reflect_1d, ops.cpp:7784-7815 (shape rule and asserts: ggml_pad_reflect_1d, ggml.c:5072-5099):
+//   a row is src[p0], .., src[1], src[0 .. ne00 - 1], src[ne00 - 2], .., src[ne00 - 1 - p1]; the reflected index is computed per word
+__global__ void __launch_bounds__(256) k_pad_reflect_1d(tview s, tview d, int64_t U, int p0) {
+    const int64_t n = U * d.ne[1] * d.ne[2] * d.ne[3];
+    for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
+        const tcoord c = t_unit_coord(U, d, e);
+        const int64_t j = c.i0 * 4;
+        uint32_t * drow = (uint32_t *) d.data + (e / U) * d.ne[0];
+        const uint32_t * srow = (const uint32_t *) t_row_at(s, c);
+        const int cnt = d.ne[0] - j < 4 ? (int)(d.ne[0] - j) : 4;
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            int64_t i = j + k - p0;
+            i = i < 0 ? -i : (i >= s.ne[0] ? 2 * (s.ne[0] - 1) - i : i);
+            v[k] = 0;
+            if (k < cnt) v[k] = srow[i];
+        }
+        pad_store4(drow + j, ((uintptr_t) drow & 15) == 0, cnt, v);
+    }
+}
+extern "C" int cllm_op_pad_reflect_1d(void * stream, const cllm_tensor * src, cllm_tensor * dst, int p0, int p1) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "pad_reflect_1d: null");
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "pad_reflect_1d: type (F32 only)");
+    if (p0 < 0 || p1 < 0) FAIL(CLLM_E_INVALID, "pad_reflect_1d: negative padding");
+    if (p0 >= src->ne[0] || p1 >= src->ne[0]) FAIL(CLLM_E_INVALID, "pad_reflect_1d: padding must be smaller than the row");      // the constructor's asserts
+    if (dst->ne[0] != src->ne[0] + p0 + p1 || dst->ne[1] != src->ne[1] || dst->ne[2] != src->ne[2] || dst->ne[3] != src->ne[3]) FAIL(CLLM_E_INVALID, "pad_reflect_1d: shape");
+    if (!t_is_contiguous(src) || !t_is_contiguous(dst)) FAIL(CLLM_E_UNSUPPORTED, "pad_reflect_1d: src and dst must be contiguous");
+    if (((uintptr_t) src->data | (uintptr_t) dst->data) % 4) FAIL(CLLM_E_UNSUPPORTED, "pad_reflect_1d: alignment");
+    if (t_nelements(dst) == 0) return CLLM_OK;
+    const int64_t U = (dst->ne[0] + 3) / 4;
+    hipLaunchKernelGGL(k_pad_reflect_1d, dim3(grid_1d(U * t_nrows(dst), 16384)), dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), U, p0);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// UPSCALE   ggml_compute_forward_upscale_f32, ops.cpp:7478-7672, its NEAREST and plain BILINEAR branches (what ggml::interpolate emits: no align-corners, no antialias).
+//   sf_k = (float) ne_k / ne0k (a float division, done once on the host); one thread per dst element; the source through its four byte strides.
+//   NEAREST:  i0k = (int64_t)(i_k / sf_k) on all four axes: the IEEE quotient, truncated
+//   BILINEAR: axes 2 and 3 as in NEAREST; on axes 0 and 1 x = ((float) i + 0.5f) / sf - 0.5f, x0 = floorf(x), x1 = x0 + 1, both clamped to [0, ne0k - 1], dx = x - (float)(the
+//             clamped x0) clamped to [0, 1] by std::max(0.0f, std::min(dx, 1.0f)).  a*(1-dx)*(1-dy) + b*dx*(1-dy) + c*(1-dx)*dy + d*dx*dy as gcc -O2 -march=x86-64-v3
+//             compiles it (read from libggml-cpu.so, pinned by tests/test_resample_model.py): the four products with dx / (1 - dx) are rounded, b's product with (1 - dy)
+//             is rounded too, and the other three enter as fmas in the order a, c, d.
+// An index is kept inside the source where float rounding could carry the reference's own past its end (ne beyond 2^23): no word changes where the reference reads inside.
+struct upscale_geom { float sf0, sf1, sf2, sf3; };
+__device__ __forceinline__ int64_t upscale_near(int64_t i, float sf, int64_t ne) { const int64_t k = (int64_t) __fdiv_rn((float) i, sf); return k < ne ? k : ne - 1; }
+__device__ __forceinline__ void upscale_lin(int64_t i, float sf, int64_t ne, int64_t & k0, int64_t & k1, float & dk) {
+    const float x = __fdiv_rn((float) i + 0.5f, sf) - 0.5f;
+    k0 = (int64_t) floorf(x); k1 = k0 + 1;
+    k0 = k0 > ne - 1 ? ne - 1 : k0; k0 = k0 < 0 ? 0 : k0;
+    k1 = k1 > ne - 1 ? ne - 1 : k1; k1 = k1 < 0 ? 0 : k1;
+    dk = x - (float) k0;
+    dk = 1.0f < dk ? 1.0f : dk;          // std::min(dk, 1.0f)
+    dk = 0.0f < dk ? dk : 0.0f;          // std::max(0.0f, .)
+}
+template <int MODE>      // 0: NEAREST, 1: BILINEAR (== enum ggml_scale_mode)
+__global__ void __launch_bounds__(256) k_upscale(tview s, tview d, upscale_geom G) {
+    const int64_t n = d.ne[0] * d.ne[1] * d.ne[2] * d.ne[3];
+    for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
+        const tcoord c = t_elem_coord(d, e);
+        const char * plane = s.data + upscale_near(c.i2, G.sf2, s.ne[2]) * s.nb[2] + upscale_near(c.i3, G.sf3, s.ne[3]) * s.nb[3];
+        if (MODE == 0) {
+            ((uint32_t *) d.data)[e] = *(const uint32_t *)(plane + upscale_near(c.i0, G.sf0, s.ne[0]) * s.nb[0] + upscale_near(c.i1, G.sf1, s.ne[1]) * s.nb[1]);
+        } else {
+            int64_t x0, x1, y0, y1; float dx, dy;
+            upscale_lin(c.i0, G.sf0, s.ne[0], x0, x1, dx);
+            upscale_lin(c.i1, G.sf1, s.ne[1], y0, y1, dy);
+            const float a = *(const float *)(plane + x0 * s.nb[0] + y0 * s.nb[1]), b = *(const float *)(plane + x1 * s.nb[0] + y0 * s.nb[1]);
+            const float cc = *(const float *)(plane + x0 * s.nb[0] + y1 * s.nb[1]), dd = *(const float *)(plane + x1 * s.nb[0] + y1 * s.nb[1]);
+            const float mx = 1.0f - dx, my = 1.0f - dy;
+            float v = (b * dx) * my;
+            v = __builtin_fmaf(a * mx, my, v);
+            v = __builtin_fmaf(cc * mx, dy, v);
+            v = __builtin_fmaf(dd * dx, dy, v);
+            ((float *) d.data)[e] = v;
+        }
+    }
+}
+extern "C" int cllm_op_upscale(void * stream, const cllm_tensor * src, cllm_tensor * dst, int mode_flags) {
+    if (!src || !dst) FAIL(CLLM_E_INVALID, "upscale: null");
+    if (src->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32) FAIL(CLLM_E_UNSUPPORTED, "upscale: type (F32 only)");
+    if (mode_flags != 0 && mode_flags != 1) FAIL(CLLM_E_UNSUPPORTED, "upscale: mode %#x (NEAREST and BILINEAR without flags only)", (unsigned) mode_flags);
+    if (!t_is_contiguous(dst)) FAIL(CLLM_E_UNSUPPORTED, "upscale: dst must be contiguous");
+    if (((uintptr_t) src->data | (uintptr_t) dst->data | src->nb[0] | src->nb[1] | src->nb[2] | src->nb[3]) % 4) FAIL(CLLM_E_UNSUPPORTED, "upscale: alignment");
+    for (int i = 0; i < 4; i++) if (dst->ne[i] < 0 || src->ne[i] < 0) FAIL(CLLM_E_INVALID, "upscale: shape");
+    if (t_nelements(dst) == 0) return CLLM_OK;
+    if (t_nelements(src) == 0) FAIL(CLLM_E_INVALID, "upscale: shape (an empty source)");
+    const upscale_geom G = { (float) dst->ne[0] / src->ne[0], (float) dst->ne[1] / src->ne[1], (float) dst->ne[2] / src->ne[2], (float) dst->ne[3] / src->ne[3] };
+    const dim3 grid(grid_1d(t_nelements(dst), 16384));
+    if (mode_flags == 0) hipLaunchKernelGGL(k_upscale<0>, grid, dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), G);
+    else                 hipLaunchKernelGGL(k_upscale<1>, grid, dim3(256), 0, (hipStream_t) stream, tv(src), tv(dst), G);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}
+
+// CONV_TRANSPOSE_1D     ggml_compute_forward_conv_transpose_1d_f16_f32 / _f32, ops.cpp:5915-6089 (shape rule and asserts: ggml_conv_transpose_1d, ggml.c:4501-4529).
+//   kernel a [K, Cout, Cin] F16 | F32, data b [L, Cin] F32, dst [(L - 1) * s0 + K, Cout] F32.  Per output row oc, from +0.0f: for i10 ascending, for every tap i00:
+//   dst[oc][i10 * s0 + i00] += v(oc, i10, i00), v = ggml_vec_dot_f16 (the data rounded to fp16 first) or ggml_vec_dot_f32 over Cin.
+// One lane per output element (oc, t): it walks the i10 with 0 <= t - i10 * s0 < K ascending and adds their dot products in plain float adds; the reference's 32
+// accumulators (accumulator a takes ci = a, a + 32, ..., one fma each), GGML_F32x8_REDUCE's tree and the Cin mod 32 leftovers all in that lane's registers: matmul_f.hip's
+// VD order, in-lane.  No atomics, no zero-fill pass, no workspace, no repack: neighbouring lanes (neighbouring t, the same i10) read neighbouring taps a[i00, oc, ci] and
+// the same data word b[i10, ci].
+// ================================================================================================
+template <typename T> __device__ __forceinline__ float ct1d_tap(const char * p);                // a kernel element, widened
+template <> __device__ __forceinline__ float ct1d_tap<uint16_t>(const char * p) { return h2f(*(const uint16_t *) p); }
+template <> __device__ __forceinline__ float ct1d_tap<float>(const char * p)    { return *(const float *) p; }
+template <typename T> __device__ __forceinline__ float ct1d_dat(const char * p);                // a data element as the dot product sees it: F16 kernel -> fp16 (RNE) -> fp32
+template <> __device__ __forceinline__ float ct1d_dat<uint16_t>(const char * p) { return h2f(f2h(*(const float *) p)); }
+template <> __device__ __forceinline__ float ct1d_dat<float>(const char * p)    { return *(const float *) p; }
+template <typename T>
+__global__ void __launch_bounds__(256) k_conv_transpose_1d(tview a, tview b, tview d, int s0) {
+    const int64_t K = a.ne[0], Cin = a.ne[2], L = b.ne[0], OL = d.ne[0], n = OL * d.ne[1], np = Cin & ~(int64_t) 31;
+    for (int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t) gridDim.x * blockDim.x) {
+        const int64_t t = e % OL, oc = e / OL;
+        const int64_t lo = t >= K ? (t - K) / s0 + 1 : 0, hi = t / s0 < L - 1 ? t / s0 : L - 1;       // the i10 whose taps reach t
+        float out = 0.0f;
+        for (int64_t i10 = lo; i10 <= hi; i10++) {
+            const char * ap = a.data + (t - i10 * s0) * (int64_t) sizeof(T) + oc * a.nb[1];
+            const char * bp = b.data + i10 * 4;
+            float acc[32];
+#pragma unroll
+            for (int j = 0; j < 32; j++) acc[j] = 0.0f;
+            for (int64_t c0 = 0; c0 < np; c0 += 32) {
+#pragma unroll
+                for (int j = 0; j < 32; j++) acc[j] = __builtin_fmaf(ct1d_dat<T>(bp + (c0 + j) * b.nb[1]), ct1d_tap<T>(ap + (c0 + j) * a.nb[2]), acc[j]);
+            }
+            // GGML_F32x8_REDUCE (simd-mappings.h:549-567) over accumulator 8 r + l of register r: x0 += x2, x1 += x3; x0 += x1; low half + high half; hadd, hadd
+            float h[4];
+#pragma unroll
+            for (int l = 0; l < 4; l++) h[l] = ((acc[l] + acc[16 + l]) + (acc[8 + l] + acc[24 + l])) + ((acc[4 + l] + acc[20 + l]) + (acc[12 + l] + acc[28 + l]));
+            float u = (h[0] + h[1]) + (h[2] + h[3]);
+            if (sizeof(T) == 2) {
+                double sd = (double) u;           // ggml_vec_dot_f16's leftovers: float products added in double, rounded once
+                for (int64_t ci = np; ci < Cin; ci++) sd += (double)(ct1d_dat<T>(bp + ci * b.nb[1]) * ct1d_tap<T>(ap + ci * a.nb[2]));
+                u = (float) sd;
+            } else {
+                // ggml_vec_dot_f32's `sumf += x[i]*y[i]` as gcc compiles it (matmul_f.hip:93-103): whole groups of 4 as rounded products added in order, the scalar rest as fmas
+                int64_t ci = np;
+                for (; ci + 4 <= Cin; ci += 4) for (int l = 0; l < 4; l++) u = u + ct1d_dat<T>(bp + (ci + l) * b.nb[1]) * ct1d_tap<T>(ap + (ci + l) * a.nb[2]);
+                for (; ci < Cin; ci++) u = __builtin_fmaf(ct1d_dat<T>(bp + ci * b.nb[1]), ct1d_tap<T>(ap + ci * a.nb[2]), u);
+            }
+            out = out + u;
+        }
+        ((float *) d.data)[e] = out;
+    }
+}
+extern "C" int cllm_op_conv_transpose_1d(void * stream, const cllm_tensor * kernel, const cllm_tensor * data, cllm_tensor * dst, int s0) {
+    if (!kernel || !data || !dst) FAIL(CLLM_E_INVALID, "conv_transpose_1d: null");
+    if ((kernel->type != CLLM_TYPE_F16 && kernel->type != CLLM_TYPE_F32) || data->type != CLLM_TYPE_F32 || dst->type != CLLM_TYPE_F32)
+        FAIL(CLLM_E_UNSUPPORTED, "conv_transpose_1d: type (F16 | F32 kernel, F32 data and dst)");
+    if (s0 <= 0) FAIL(CLLM_E_INVALID, "conv_transpose_1d: stride");
+    const size_t es = cllm_type_size(kernel->type);
+    if (kernel->nb[0] != es || data->nb[0] != 4) FAIL(CLLM_E_UNSUPPORTED, "conv_transpose_1d: rows must be dense");      // the reference's asserts on nb00 and nb10
+    const int64_t K = kernel->ne[0], Cout = kernel->ne[1], Cin = kernel->ne[2], L = data->ne[0];
+    if (kernel->ne[3] != 1 || data->ne[2] != 1 || data->ne[3] != 1 || data->ne[1] != Cin || K < 0 || Cout < 0 || Cin < 0 || L < 0) FAIL(CLLM_E_INVALID, "conv_transpose_1d: shape (kernel against data)");
+    if (dst->ne[0] != (L - 1) * s0 + K || dst->ne[1] != Cout || dst->ne[2] != 1 || dst->ne[3] != 1) FAIL(CLLM_E_INVALID, "conv_transpose_1d: shape (dst)");
+    if (!t_is_contiguous(dst)) FAIL(CLLM_E_UNSUPPORTED, "conv_transpose_1d: dst must be contiguous");
+    if (((uintptr_t) kernel->data | kernel->nb[1] | kernel->nb[2]) % es || ((uintptr_t) data->data | (uintptr_t) dst->data | data->nb[1]) % 4) FAIL(CLLM_E_UNSUPPORTED, "conv_transpose_1d: alignment");
+    if (t_nelements(dst) == 0) return CLLM_OK;
+    const dim3 grid(grid_1d(t_nelements(dst), 16384));
+    hipStream_t st = (hipStream_t) stream;
+    if (kernel->type == CLLM_TYPE_F16) hipLaunchKernelGGL((k_conv_transpose_1d<uint16_t>), grid, dim3(256), 0, st, tv(kernel), tv(data), tv(dst), s0);
+    else                               hipLaunchKernelGGL((k_conv_transpose_1d<float>),    grid, dim3(256), 0, st, tv(kernel), tv(data), tv(dst), s0);
+    LAUNCH_CHECK();
+    return CLLM_OK;
+}

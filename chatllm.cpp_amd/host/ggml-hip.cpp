@@ -471,6 +471,34 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
                    a->ne[0] + 2 * (int64_t) q[5] + q[1] <= 0x7fffffff && a->ne[1] + 2 * (int64_t) q[6] + q[2] <= 0x7fffffff &&
                    op->ne[0] == out(a->ne[0], q[1], q[3], q[5]) && op->ne[1] == out(a->ne[1], q[2], q[4], q[6]);
         }
+        // the four cases below restate cllm_op_pad / _pad_reflect_1d / _upscale / _conv_transpose_1d's own predicates, with two exceptions that hold for every tensor of a
+        // graph: the entries' tests of the data pointers (every one of the four tests them for 4-byte or element alignment) are left out, because this module's buffers
+        // are 256-byte aligned, ggml-alloc keeps that alignment and the host cuts its views at whole elements (a pointer that is off all the same fails the entry, and with it graph_compute); and cllm_op_upscale's ne >= 0 is left out,
+        // because a ggml tensor has no negative ne.  dst ne is the constructor's
+        case GGML_OP_PAD: {        // lp0, rp0, .., lp3, rp3, circular
+            const int32_t * q = op->op_params;
+            if (!a || a->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_is_contiguous(op) || q[8] != 0) return false;
+            for (int i = 0; i < 4; i++) if (q[2 * i] < 0 || q[2 * i + 1] < 0 || op->ne[i] != a->ne[i] + q[2 * i] + q[2 * i + 1] || a->nb[i] % 4) return false;
+            return true;
+        }
+        case GGML_OP_PAD_REFLECT_1D: {
+            const int32_t * q = op->op_params;      // p0, p1
+            return a && a->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && ggml_is_contiguous(a) && ggml_is_contiguous(op) && q[0] >= 0 && q[1] >= 0 && q[0] < a->ne[0] && q[1] < a->ne[0] &&
+                   op->ne[0] == a->ne[0] + q[0] + q[1] && op->ne[1] == a->ne[1] && op->ne[2] == a->ne[2] && op->ne[3] == a->ne[3];
+        }
+        case GGML_OP_UPSCALE: {    // op_params[0]: the mode and its flag bits; NEAREST and BILINEAR with no flag (what ggml::interpolate emits), align-corners, antialias and bicubic stay on the CPU
+            const int32_t mode = op->op_params[0];
+            if (!a || a->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_is_contiguous(op) || (mode != GGML_SCALE_MODE_NEAREST && mode != GGML_SCALE_MODE_BILINEAR)) return false;
+            return a->nb[0] % 4 == 0 && a->nb[1] % 4 == 0 && a->nb[2] % 4 == 0 && a->nb[3] % 4 == 0 && (ggml_nelements(op) == 0 || ggml_nelements(a) != 0);
+        }
+        case GGML_OP_CONV_TRANSPOSE_1D: {      // a: the kernel [K, Cout, Cin], b: the data [L, Cin]; op_params: s0, p0, d0
+            const int32_t * q = op->op_params;
+            if (!a || !b || (a->type != GGML_TYPE_F16 && a->type != GGML_TYPE_F32) || !f32_dense(b) || op->type != GGML_TYPE_F32 || !dense_rows(a) || !ggml_is_contiguous(op)) return false;
+            if (q[0] <= 0 || q[1] != 0 || q[2] != 1) return false;
+            const size_t es = ggml_type_size(a->type);
+            return a->ne[3] == 1 && b->ne[2] == 1 && b->ne[3] == 1 && b->ne[1] == a->ne[2] && op->ne[0] == (b->ne[0] - 1) * q[0] + a->ne[0] && op->ne[1] == a->ne[1] && op->ne[2] == 1 && op->ne[3] == 1 &&
+                   a->nb[1] % es == 0 && a->nb[2] % es == 0 && b->nb[1] % 4 == 0;
+        }
         case GGML_OP_GET_ROWS: return (is_q(a->type) || is_kq(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) && b->type == GGML_TYPE_I32 && op->type == GGML_TYPE_F32;
         default: return false;
     }
@@ -1035,6 +1063,10 @@ ggml_status walk(walk_ctx & w, fuse_plan & plan, sig_writer * sw) {
             case GGML_OP_IM2COL:         { const int32_t * q = n->op_params; rc = E(cllm_op_im2col, st, &da, &db, &d, (int) q[0], (int) q[1], (int) q[2], (int) q[3], (int) q[4], (int) q[5], (int) q[6]); } break;
             case GGML_OP_POOL_1D:        { const int32_t * q = n->op_params; rc = E(cllm_op_pool_1d, st, (int) q[0], &da, &d, (int) q[1], (int) q[2], (int) q[3]); } break;      // cllm_pool == ggml_op_pool
             case GGML_OP_POOL_2D:        { const int32_t * q = n->op_params; rc = E(cllm_op_pool_2d, st, (int) q[0], &da, &d, (int) q[1], (int) q[2], (int) q[3], (int) q[4], (int) q[5], (int) q[6]); } break;
+            case GGML_OP_PAD:            { const int32_t * q = n->op_params; rc = E(cllm_op_pad, st, &da, &d, (int) q[0], (int) q[1], (int) q[2], (int) q[3], (int) q[4], (int) q[5], (int) q[6], (int) q[7]); } break;      // q[8] (circular) is 0: supports_op
+            case GGML_OP_PAD_REFLECT_1D: { const int32_t * q = n->op_params; rc = E(cllm_op_pad_reflect_1d, st, &da, &d, (int) q[0], (int) q[1]); } break;
+            case GGML_OP_UPSCALE:        rc = E(cllm_op_upscale, st, &da, &d, (int) n->op_params[0]); break;
+            case GGML_OP_CONV_TRANSPOSE_1D: rc = E(cllm_op_conv_transpose_1d, st, &da, &db, &d, (int) n->op_params[0]); break;      // p0 == 0, d0 == 1: supports_op
             default: HIPB_LOG("graph_compute: op %s reached the device although supports_op() declined it", ggml_op_name(n->op)); return GGML_STATUS_FAILED;
         }
         if (rc != CLLM_OK) {

@@ -138,6 +138,10 @@ SIGNATURES = {
     "cllm_op_im2col": (C.c_int, [_P, _T, _T, _T] + [C.c_int] * 7),
     "cllm_op_pool_1d": (C.c_int, [_P, C.c_int, _T, _T] + [C.c_int] * 3),
     "cllm_op_pool_2d": (C.c_int, [_P, C.c_int, _T, _T] + [C.c_int] * 6),
+    "cllm_op_pad": (C.c_int, [_P, _T, _T] + [C.c_int] * 8),
+    "cllm_op_pad_reflect_1d": (C.c_int, [_P, _T, _T, C.c_int, C.c_int]),
+    "cllm_op_upscale": (C.c_int, [_P, _T, _T, C.c_int]),
+    "cllm_op_conv_transpose_1d": (C.c_int, [_P, _T, _T, _T, C.c_int]),
     "cllm_op_quantize_rows": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int64]),
     "cllm_dequantize_row": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64]),
     "cllm_llama_create": (C.c_int, [C.POINTER(LlamaConfig), _P, C.POINTER(C.c_void_p)]),

@@ -377,5 +377,40 @@ def conv_2d(kernel, data, s0, s1, p0, p1, d0, d1):
     return cont(out.reshape(col.ne[1], col.ne[2], col.ne[3], kernel.ne[3]).permute(0, 1, 3, 2))
 
 
+SCALE_NEAREST, SCALE_BILINEAR = 0, 1      # == enum ggml_scale_mode; no flag bits (ggml::interpolate sets none)
+
+
+def pad(a, lp0, rp0, lp1=0, rp1=0, lp2=0, rp2=0, lp3=0, rp3=0, dst=None):
+    """ggml::pad (ggml_pad_ext): zeros to the left and right of every axis; a may be any F32 view"""
+    dst = dst or Tensor(F32, [a.ne[0] + lp0 + rp0, a.ne[1] + lp1 + rp1, a.ne[2] + lp2 + rp2, a.ne[3] + lp3 + rp3])
+    _l.check(_l.get().cllm_op_pad(None, _ref(a), _ref(dst), lp0, rp0, lp1, rp1, lp2, rp2, lp3, rp3), "pad")
+    return dst
+
+
+def pad_reflect_1d(a, p0, p1, dst=None):
+    """ggml::pad_reflect (ggml_pad_reflect_1d): [ne00, ...] -> [p0 + ne00 + p1, ...], mirrored around the first and the last element"""
+    dst = dst or Tensor(F32, [a.ne[0] + p0 + p1, a.ne[1], a.ne[2], a.ne[3]])
+    _l.check(_l.get().cllm_op_pad_reflect_1d(None, _ref(a), _ref(dst), p0, p1), "pad_reflect_1d")
+    return dst
+
+
+def upscale(a, mode, ne=None, scale_factor=None, dst=None):
+    """ggml::interpolate (ggml_interpolate) with mode SCALE_NEAREST | SCALE_BILINEAR: to the destination `ne`, or, as the host's convenience form does, to
+    [int(ne0 * scale_factor), int(ne1 * scale_factor), ne2, ne3]"""
+    if dst is None:
+        if ne is None:
+            ne = [int(a.ne[0] * scale_factor), int(a.ne[1] * scale_factor), a.ne[2], a.ne[3]]
+        dst = Tensor(F32, list(ne) + [1] * (4 - len(ne)))
+    _l.check(_l.get().cllm_op_upscale(None, _ref(a), _ref(dst), mode), "upscale")
+    return dst
+
+
+def conv_transpose_1d(kernel, data, s0, dst=None):
+    """ConvTransposed1D::forward's node (ggml_conv_transpose_1d with padding 0, dilation 1): kernel [K, Cout, Cin] F16 | F32, data [L, Cin] F32 -> [(L - 1) * s0 + K, Cout]"""
+    dst = dst or Tensor(F32, [(data.ne[0] - 1) * s0 + kernel.ne[0], kernel.ne[1], 1, 1])
+    _l.check(_l.get().cllm_op_conv_transpose_1d(None, _ref(kernel), _ref(data), _ref(dst), s0), "conv_transpose_1d")
+    return dst
+
+
 def sync():
     _l.check(_l.get().cllm_stream_sync(None), "sync")

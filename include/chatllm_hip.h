@@ -391,6 +391,25 @@ typedef enum cllm_pool { CLLM_POOL_MAX = 0, CLLM_POOL_AVG = 1 } cllm_pool;
  * An empty tensor: CLLM_OK, no launch.  A declined call leaves dst untouched. */
 CLLM_API int cllm_op_pool_1d(void * stream, int op /* cllm_pool */, const cllm_tensor * src, cllm_tensor * dst, int k0, int s0, int p0);
 CLLM_API int cllm_op_pool_2d(void * stream, int op /* cllm_pool */, const cllm_tensor * src, cllm_tensor * dst, int k0, int k1, int s0, int s1, int p0, int p1);
+/* The nodes the audio and vision front ends put around their convolutions.  All four: F32 data, a contiguous dst, every word with the bits of the reference's CPU build;
+ * CLLM_E_INVALID: null, shapes, parameter ranges; CLLM_E_UNSUPPORTED: types, strides, modes.  An empty dst: CLLM_OK, no launch.  A declined call leaves dst untouched.
+ * GGML_OP_PAD           ggml_compute_forward_pad_f32<false> (ggml-cpu/ops.cpp:7696-7758; shape rule ggml_pad_ext, ggml.c:5016-5049): dst ne[k] == src ne[k] + lpk + rpk, pads >= 0;
+ *   inside [lp, ne - rp) on all four axes the source word (NaN payloads untouched), +0.0f elsewhere.  src through all four byte strides (nb[0] too; multiples of 4).
+ *   The circular form (ggml_pad_ext_circular) has no entry: the module declines it. */
+CLLM_API int cllm_op_pad(void * stream, const cllm_tensor * src, cllm_tensor * dst, int lp0, int rp0, int lp1, int rp1, int lp2, int rp2, int lp3, int rp3);
+/* GGML_OP_PAD_REFLECT_1D    ggml_compute_forward_pad_reflect_1d (ggml-cpu/ops.cpp:7784-7815; shape rule and asserts ggml_pad_reflect_1d, ggml.c:5072-5099): 0 <= p0, p1 < src ne[0],
+ *   src contiguous (as the constructor asserts); a dst row is src[p0], .., src[1], src[0 .. ne00 - 1], src[ne00 - 2], .., src[ne00 - 1 - p1]. */
+CLLM_API int cllm_op_pad_reflect_1d(void * stream, const cllm_tensor * src, cllm_tensor * dst, int p0, int p1);
+/* GGML_OP_UPSCALE       ggml_compute_forward_upscale_f32 (ggml-cpu/ops.cpp:7478-7672; ggml_interpolate, ggml.c:4939-4990): mode_flags is the node's op_params[0] and must be
+ *   GGML_SCALE_MODE_NEAREST (0) or GGML_SCALE_MODE_BILINEAR (1) with no flag bit: what ggml::interpolate emits.  Align-corners, antialias and bicubic: CLLM_E_UNSUPPORTED.
+ *   dst of any ne; sf_k = (float) ne_k / src ne_k; NEAREST reads src[(int64_t)(i_k / sf_k)] on every axis; BILINEAR does so on axes 2 and 3 and interpolates on 0 and 1 with
+ *   the pixel offset 0.5, clamped indices, dx from the clamped index, and the reference build's fma pattern.  src through all four byte strides. */
+CLLM_API int cllm_op_upscale(void * stream, const cllm_tensor * src, cllm_tensor * dst, int mode_flags);
+/* GGML_OP_CONV_TRANSPOSE_1D     ggml_compute_forward_conv_transpose_1d_f16_f32 / _f32 (ggml-cpu/ops.cpp:5915-6089; shape rule and asserts ggml_conv_transpose_1d, ggml.c:4501-4529),
+ *   padding 0 and dilation 1 as there.  kernel [K, Cout, Cin, 1] F16 | F32 with nb[0] == its element size (nb[1], nb[2] as given), data [L, Cin] F32 with nb[0] == 4 (nb[1] as
+ *   given), dst [(L - 1) * s0 + K, Cout, 1, 1], s0 > 0.  dst[oc][t] = ((+0.0f + v(i10_min)) + v(i10_min + 1)) + .. over the i10 with 0 <= t - i10 * s0 < K, ascending;
+ *   v = ggml_vec_dot_f16 (F16 kernel: the data rounded to fp16 first) or ggml_vec_dot_f32 over Cin, in the order of the reference's AVX2 build. */
+CLLM_API int cllm_op_conv_transpose_1d(void * stream, const cllm_tensor * kernel, const cllm_tensor * data, cllm_tensor * dst, int s0);
 /* WEIGHT quantizers on the device: quantize_row_{q8_0,q4_0,q4_1,q5_0,q5_1,q4_K}_ref and the F16 conversion (ggml/src/ggml-quants.c:36-222, 622-702, 1280-1350),
  * byte-identical to the reference's from_float_ref.  Replaces the host-side loop of ggml::from_float (src/layers.cpp:358-373) that chatllm.cpp's loader runs when a
  * tensor is re-quantized on load (src/chat.cpp:1246-1279): nrows rows of k fp32 values at x (device, contiguous, 16-byte aligned) -> rows of `type` blocks at y. */
