@@ -1,338 +1,6 @@
-// fattn.hip -- GGML_OP_FLASH_ATTN_EXT and the same tiled kernel behind the prefill attention block: the score matrix never
-// leaves the CU.
-//
-//   out[:, h, n] = sum_kv softmax_kv(scale * K[kv, h/r] . Q[n, h] + mask[kv, n]) * V[kv, h/r]
-//   ggml_compute_forward_flash_attn_ext_f16 (ggml-cpu/ops.cpp:8114-8344 one query at a time, :8346-8640 tiled, :8642-8710 the
-//   split-KV reduction); used by CoreAttention with `-fa` (src/layers.cpp:2634-2656) over the K / V caches of
-//   src/layers.cpp:2925-2945 (F16, or Q8_0 with --cache_dtype q8_0).
-//
-// Numerics: TOLERANCE tier.  The CPU op itself has three summation orders (one_chunk / tiled / split-KV, chosen by shape and
-// thread count), so there is no single bit pattern to match.  What is kept from the CPU path: Q is converted to K's
-// vec_dot_type first (F16 K: rounded to fp16; Q8_0 K: quantize_row_q8_0, i.e. the 8-bit rounding of Q is reproduced), K / V
-// are used at their stored precision, products are exact in fp32, the soft-max runs in fp32 (online, base 2).  What differs:
-// P is rounded to fp16 before the P.V product (the CPU keeps it in fp32 but accumulates V in fp16 for an F16 cache), and
-// accumulation is in MFMA order.
-//
-// One kernel, v_mfma_f32_32x32x16_f16, "swapped" form so that every soft-max quantity of a query row lives in one lane pair:
-//   S^T[kv, q] = K[kv, :] . Q[q, :]      A = K tile (LDS, XOR-swizzled rows), B = Q (registers, loaded once)
-//   lane (l31, hi) holds S^T[kv = crow(r, hi) + 32 j, q = l31], crow(r, hi) = (r & 3) + 8 (r >> 2) + 4 hi
-//   O^T[dv, q] += Vt[dv, kv] . P^T[kv, q]  A = V^T tile (LDS, [dv][kv] rows), B = P: exactly the registers the lane already
-//   holds (the contraction order of an MFMA is free as long as A and B agree), so P never moves between lanes.
-// A workgroup is NW waves x 32 query rows over one (kv head | head); K/V tiles of 64 positions are staged through LDS by all
-// waves.  Decode (few rows): the r heads of a GQA group are packed as rows of one tile (R = r) so K/V are read once per
-// group, NW = 1, and the positions are split over gridDim.x workgroups whose partial (m, l, O) are merged by k_fattn_merge.
+// fattn.hip -- flash attention's entry points (launch_fattn: validation and the split plan for every head size; launch_attn_long_flash: the
+// long-context decode step) and the instantiations of k_fattn (fattn.h) at head sizes 64 and 128; 96 and 256 are fattn_hs.hip.
 #include "fattn.h"
-
-template <int D, int KVT, int VL, int MASK, int NW>
-__global__ void __launch_bounds__(NW * 64, 2) k_fattn(const fattn_args a) {
-    constexpr int NT = NW * 64, BQ = NW * 32, KS = D / 16, NB = D / 32, CPR = D / 8;
-    extern __shared__ __attribute__((aligned(16))) char fa_smem[];
-    char * Kl = fa_smem, * Vl = fa_smem + 64 * D * 2;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int rows = a.N * a.R, nqb = (rows + BQ - 1) / BQ;
-    int qb = (int) blockIdx.x % nqb;
-    const int split = (int) blockIdx.x / nqb;
-    if (MASK == 1) qb = nqb - 1 - qb;                                  // the long (late) query blocks first
-    const int y = blockIdx.y, b = blockIdx.z;
-    const int hk = y * a.R / (a.H / a.Hkv);
-    const bool wave_live = qb * BQ + wave * 32 < rows;
-    const int rho = qb * BQ + wave * 32 + l31;
-    const bool rvalid = rho < rows;
-    const int rc = rvalid ? rho : rows - 1;
-    const int n = rc / a.R, h = y * a.R + rc % a.R;
-
-    // ---- Q: 16 ks fragments of 8 halves (dk = 16 ks + 8 hi ..), converted as the CPU converts it for K's vec_dot
-    half8 qf[KS];
-    {
-        const char * qp = a.q + (int64_t) n * a.q_nb1 + (int64_t) h * a.q_nb2 + (int64_t) b * a.q_nb3;
-        float x[KS][8];
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) {
-            const f32x4 lo = *(const f32x4 *)(qp + (16 * ks + 8 * hi) * 4), up = *(const f32x4 *)(qp + (16 * ks + 8 * hi) * 4 + 16);
-            x[ks][0] = lo.x; x[ks][1] = lo.y; x[ks][2] = lo.z; x[ks][3] = lo.w; x[ks][4] = up.x; x[ks][5] = up.y; x[ks][6] = up.z; x[ks][7] = up.w;
-        }
-        if (KVT == CLLM_TYPE_Q8_0) {                                   // quantize_row_q8_0 (arch/x86/quants.c:290-345) then the dequantized value
-#pragma unroll
-            for (int blk = 0; blk < D / 32; blk++) {
-                float amax = 0.0f;
-#pragma unroll
-                for (int e = 0; e < 8; e++) amax = fmaxf(amax, fmaxf(fabsf(x[2 * blk][e]), fabsf(x[2 * blk + 1][e])));
-                amax = fa_pair_max(amax);
-                const float d = amax / 127.0f, id = amax != 0.0f ? 127.0f / amax : 0.0f, dq = h2f(f2h(d));
-#pragma unroll
-                for (int e = 0; e < 8; e++) { x[2 * blk][e] = dq * rintf(x[2 * blk][e] * id); x[2 * blk + 1][e] = dq * rintf(x[2 * blk + 1][e] * id); }
-            }
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) qf[ks][e] = (_Float16) x[ks][e];
-    }
-
-    const char * kb = a.k + (int64_t) hk * a.k_nb2 + (int64_t) b * a.k_nb3;
-    const char * vb = a.v + (int64_t) hk * a.v_nb2 + (int64_t) b * a.v_nb3;
-    const char * mrow = MASK == 2 ? a.mask + (int64_t) n * a.m_nb1 + (int64_t)(h % a.m_ne2) * a.m_nb2 + (int64_t)(b % a.m_ne3) * a.m_nb3 : nullptr;
-
-    const int n_kv = a.n_kv_dev ? min(a.n_kv, a.n_kv_dev[0] + 1) : a.n_kv;
-    const int kv_lo = split * a.chunk;
-    int kv_hi = min(n_kv, kv_lo + a.chunk);
-    if (MASK == 1) kv_hi = min(kv_hi, a.n_past + min(a.N - 1, (qb * BQ + BQ - 1) / a.R) + 1);
-    const int lim = MASK == 1 ? a.n_past + n : 0;                      // causal: position kv is visible to row n iff kv <= n_past + n
-
-    const float mask_mul = FA_LOG2E / a.sc2;                           // mask values are added to the RAW scores: (s + mask log2e / sc2) sc2 = s sc2 + mask log2e
-    f32x16 o[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[i][r] = 0.0f;
-    float m_run = -INFINITY, l_run = 0.0f;
-
-    // ---- K / V staging is split in two: global -> registers (issued one tile ahead: the loads fly under the MFMA work of the current tile) and
-    //      registers -> LDS (conversion, swizzle, transposition; between the two barriers of a tile).  Q8_0 rows keep their raw 16-bit pieces in
-    //      the registers (34-byte blocks: 2-byte alignment) and are dequantized on the way into LDS.
-    constexpr bool Q8 = KVT == CLLM_TYPE_Q8_0;
-    constexpr int NKC = (64 * CPR + NT - 1) / NT;                     // K chunks (8 elements) per thread
-    constexpr int NVU = VL == 1 ? (D * 8 + NT - 1) / NT : (16 * CPR + NT - 1) / NT;      // V^T chunks (VL 1) / 4-row x 8-element units (VL 0) per thread
-    struct raw8 { uint32_t h[4]; uint32_t d; };                      // Q8_0: four 16-bit pieces of 8 quants + the block scale
-    u32x4 kreg[Q8 ? 1 : NKC]; raw8 kraw[Q8 ? NKC : 1];
-    u32x4 vreg[Q8 ? 1 : (VL == 1 ? NVU : 4 * NVU)]; raw8 vraw[Q8 ? 4 * NVU : 1];
-    auto q8_load = [&](const char * row, int e0) {
-        raw8 r; const char * p = row + (e0 >> 5) * 34;
-        r.d = *(const uint16_t *) p;
-        const uint16_t * qs = (const uint16_t *)(p + 2 + (e0 & 31));
-#pragma unroll
-        for (int i = 0; i < 4; i++) r.h[i] = qs[i];
-        return r;
-    };
-    auto q8_cvt = [&](const raw8 & r) {
-        const float d = h2f((uint16_t) r.d);
-        u32x4 out;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const _Float16 lo = (_Float16)(d * (float)(int8_t)(r.h[i] & 0xff)), up = (_Float16)(d * (float)(int8_t)(r.h[i] >> 8));
-            uint16_t x, y; __builtin_memcpy(&x, &lo, 2); __builtin_memcpy(&y, &up, 2);
-            out[i] = (uint32_t) x | ((uint32_t) y << 16);
-        }
-        return out;
-    };
-    auto load_tile = [&](int kv0) {
-#pragma unroll
-        for (int t = 0; t < NKC; t++) {
-            const int c = tid + t * NT, row = c / CPR, col = c % CPR, kv = min(kv0 + (c < 64 * CPR ? row : 0), kv_hi - 1);
-            if (Q8) kraw[Q8 ? t : 0] = q8_load(kb + (int64_t) kv * a.k_nb1, col * 8);
-            else    kreg[Q8 ? 0 : t] = *(const u32x4 *)(kb + (int64_t) kv * a.k_nb1 + col * 16);
-        }
-        if (VL == 1) {
-#pragma unroll
-            for (int t = 0; t < NVU; t++) {
-                const int c = tid + t * NT, dv = (c >> 3) % D, kc = c & 7, kvs = kv0 + 8 * kc;
-                const int kvl = min(kvs, (n_kv - 1) & ~7);
-                vreg[Q8 ? 0 : t] = *(const u32x4 *)(vb + (int64_t) dv * a.v_nb1 + (int64_t) kvl * 2);
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < NVU; t++) {
-                const int u = (tid + t * NT) % (16 * CPR), kvg = u / CPR, dvg = u % CPR;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int kv = min(kv0 + 4 * kvg + i, kv_hi - 1);
-                    if (Q8) vraw[Q8 ? 4 * t + i : 0] = q8_load(vb + (int64_t) kv * a.v_nb1, dvg * 8);
-                    else    vreg[Q8 ? 0 : 4 * t + i] = *(const u32x4 *)(vb + (int64_t) kv * a.v_nb1 + dvg * 16);
-                }
-            }
-        }
-    };
-    auto store_tile = [&](int kv0) {
-#pragma unroll
-        for (int t = 0; t < NKC; t++) {
-            const int c = tid + t * NT, row = c / CPR, col = c % CPR;
-            if ((64 * CPR) % NT == 0 || c < 64 * CPR) *(u32x4 *)(Kl + row * (D * 2) + ((col ^ (row & (CPR - 1))) << 4)) = Q8 ? q8_cvt(kraw[Q8 ? t : 0]) : kreg[Q8 ? 0 : t];
-        }
-        if (VL == 1) {
-#pragma unroll
-            for (int t = 0; t < NVU; t++) {
-                const int c = tid + t * NT, dv = c >> 3, kc = c & 7, kvs = kv0 + 8 * kc;
-                u32x4 x = vreg[Q8 ? 0 : t];
-                if (kv0 + 64 > n_kv) {                                 // (block-uniform: only the cache's last, partial tile)
-                    const int left = n_kv - kvs;                       // elements of this chunk that exist (the rest of the cache row is not ours: may be anything)
-#pragma unroll
-                    for (int w = 0; w < 4; w++) {
-                        const uint32_t keep = 2 * w + 1 < left ? 0xffffffffu : 2 * w < left ? 0xffffu : 0u;
-                        x[w] &= keep;
-                    }
-                }
-                if ((D * 8) % NT == 0 || c < D * 8) { char * p = Vl + dv * FA_VSTR + kc * 16; *(u32x2 *) p = u32x2{x.x, x.y}; *(u32x2 *)(p + 8) = u32x2{x.z, x.w}; }
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < NVU; t++) {
-                const int u = tid + t * NT, kvg = u / CPR, dvg = u % CPR;
-                u32x4 x[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) x[i] = Q8 ? q8_cvt(vraw[Q8 ? 4 * t + i : 0]) : vreg[Q8 ? 0 : 4 * t + i];
-                if ((16 * CPR) % NT == 0 || u < 16 * CPR) {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {                      // 4 x 4 transposition in registers: V rows by position -> V^T rows by feature
-                        const uint32_t sel = (e & 1) ? 0x07060302u : 0x05040100u;
-                        const uint32_t lo = __builtin_amdgcn_perm(x[1][e >> 1], x[0][e >> 1], sel), up = __builtin_amdgcn_perm(x[3][e >> 1], x[2][e >> 1], sel);
-                        *(u32x2 *)(Vl + (8 * dvg + e) * FA_VSTR + kvg * 8) = u32x2{lo, up};
-                    }
-                }
-            }
-        }
-    };
-
-    if (kv_lo < kv_hi) load_tile(kv_lo);
-    for (int kv0 = kv_lo; kv0 < kv_hi; kv0 += 64) {
-        // ---- the mask of this tile (tensor form): the lane's 32 positions in 8 groups of 4
-        float mv[2][16];
-        bool skip = false;
-        if (MASK == 2) {
-            int any = 0;
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const int kvb = kv0 + 32 * j + 8 * g + 4 * hi;
-                    uint16_t w[4];
-                    if (a.m_al) {
-                        u32x2 t = u32x2{0xfc00fc00u, 0xfc00fc00u};
-                        if (kvb < kv_hi) t = *(const u32x2 *)(mrow + (int64_t) kvb * 2);
-                        w[0] = (uint16_t) t.x; w[1] = (uint16_t)(t.x >> 16); w[2] = (uint16_t) t.y; w[3] = (uint16_t)(t.y >> 16);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; e++) w[e] = kvb + e < kv_hi ? *(const uint16_t *)(mrow + (int64_t)(kvb + e) * 2) : (uint16_t) 0xfc00;
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float f = kvb + e < kv_hi ? h2f(w[e]) : -INFINITY;
-                        mv[j][4 * g + e] = f * mask_mul;                   // in units of the raw score (the scale is applied later)
-                        any |= (f != -INFINITY) && rvalid;
-                    }
-                }
-            skip = !__syncthreads_or(any);                             // (also: the previous tile's fragments have been read) nothing of this tile visible: no staging, no math
-        } else {
-            __syncthreads();                                           // the previous tile's fragments have been read
-        }
-        if (!skip) store_tile(kv0);
-        if (kv0 + 64 < kv_hi) load_tile(kv0 + 64);                     // the next tile's loads fly under this tile's math
-        if (skip) continue;
-        __syncthreads();
-
-        if (!wave_live) continue;                                      // (decode: the group's rows fit one wave; the others only help staging)
-        // ---- S^T = K . Q^T.  The K fragments are read FA_PD MFMAs ahead of their use (the compiler's own order is read -> wait -> MFMA, one LDS
-        //      latency per MFMA); sched_barrier pins the order
-        f32x16 s[2];
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) s[j][r] = 0.0f;
-        {
-            auto kfrag = [&](int idx) {
-                const int row = 32 * (idx / KS) + l31, ks = idx % KS;
-                return *(const half8 *)(Kl + row * (D * 2) + (((2 * ks + hi) ^ (row & (CPR - 1))) << 4));
-            };
-            half8 kf[FA_PD];
-#pragma unroll
-            for (int p = 0; p < FA_PD; p++) kf[p] = kfrag(p);
-#pragma unroll
-            for (int idx = 0; idx < 2 * KS; idx++) {
-                __builtin_amdgcn_sched_barrier(0);
-                s[idx / KS] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[idx % FA_PD], qf[idx % KS], s[idx / KS], 0, 0, 0);
-                if (idx + FA_PD < 2 * KS) kf[idx % FA_PD] = kfrag(idx + FA_PD);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-
-        // ---- online soft-max (base 2) of the row held by this lane pair.  The exponent reference m_run follows the running maximum lazily:
-        //      it moves (and O, l are rescaled) only when a tile's maximum exceeds it by more than FA_TAU, so p <= 2^FA_TAU (fp16 holds it with the
-        //      same relative precision) and the rescale of the 64 O registers leaves the steady state of the loop
-        const bool full = MASK != 2 && kv0 + 64 <= kv_hi && (MASK == 0 || kv0 + 63 <= a.n_past + (qb * BQ + wave * 32) / a.R);      // nothing of this tile is masked for this wave
-        float mx = -INFINITY;
-        if (!full) {
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int kv = kv0 + 32 * j + fa_crow(r, hi);
-                    float t = s[j][r];
-                    if (MASK == 2) t += mv[j][r];                      // -inf beyond kv_hi
-                    else if (MASK == 1) t = (kv <= lim && kv < kv_hi) ? t : -INFINITY;
-                    else t = kv < kv_hi ? t : -INFINITY;
-                    s[j][r] = t;
-                }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) mx = fmaxf(mx, s[j][r]);
-        mx = fa_pair_max(mx) * a.sc2;                                  // sc2 > 0: the maximum of the scaled scores
-        const bool grow = mx > m_run + FA_TAU;                         // (m_run = -inf: any finite maximum)
-        if (__any(grow)) {
-            const float m_new = grow ? mx : m_run;
-            const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.0f;      // m_run = -inf -> 0
-            l_run *= alpha;
-#pragma unroll
-            for (int i = 0; i < NB; i++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) o[i][r] *= alpha;
-            m_run = m_new;
-        }
-        const float msafe = m_run == -INFINITY ? 0.0f : m_run;         // a row with nothing visible yet: every p = exp2(-inf) = 0
-        float psum = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) { const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][r], a.sc2, -msafe)); s[j][r] = p; psum += p; }
-        l_run += psum;
-
-        // ---- O^T += V^T . P^T: 4 NB MFMAs, V^T fragments read FA_PD ahead
-        {
-            half8 pb[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-#pragma unroll
-                for (int e = 0; e < 8; e++) pb[q][e] = (_Float16) s[q >> 1][8 * (q & 1) + e];
-            auto vfrag = [&](int idx) {                                // idx = 4-kv-group q (j, kk) major, dv block i minor
-                const int q = idx / NB, i = idx % NB;
-                const char * p = Vl + (32 * i + l31) * FA_VSTR + (32 * (q >> 1) + 16 * (q & 1) + 4 * hi) * 2;
-                const half4 v0 = *(const half4 *) p, v1 = *(const half4 *)(p + 16);
-                return half8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            };
-            half8 vf[FA_PD];
-#pragma unroll
-            for (int p = 0; p < FA_PD; p++) vf[p] = vfrag(p);
-#pragma unroll
-            for (int idx = 0; idx < 4 * NB; idx++) {
-                __builtin_amdgcn_sched_barrier(0);
-                o[idx % NB] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx % FA_PD], pb[idx / NB], o[idx % NB], 0, 0, 0);
-                if (idx + FA_PD < 4 * NB) vf[idx % FA_PD] = vfrag(idx + FA_PD);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-
-    // ---- epilogue: lane holds O^T[dv = 32 i + crow(r, hi), q = l31]: groups of 4 consecutive dv
-    const float l_tot = fa_pair_sum(l_run);
-    if (!rvalid) return;
-    if (a.splits == 1) {
-        const float inv = l_tot == 0.0f ? 0.0f : 1.0f / l_tot;
-        char * dp = a.dst + (int64_t) n * a.d_nbn + (int64_t) h * a.d_nbh + (int64_t) b * a.d_nbb;
-#pragma unroll
-        for (int i = 0; i < NB; i++)
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-                *(f32x4 *)(dp + (32 * i + 8 * g + 4 * hi) * 4) = f32x4{o[i][4 * g] * inv, o[i][4 * g + 1] * inv, o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv};
-    } else {
-        float * pp = a.part + ((((int64_t) b * a.H + h) * a.N + n) * a.splits + split) * (D + 4);
-#pragma unroll
-        for (int i = 0; i < NB; i++)
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-                *(f32x4 *)(pp + 32 * i + 8 * g + 4 * hi) = f32x4{o[i][4 * g], o[i][4 * g + 1], o[i][4 * g + 2], o[i][4 * g + 3]};
-        if (hi == 0) { pp[D] = m_run; pp[D + 1] = l_tot; }
-    }
-}
 
 static int g_flash_min = -1;             // -1: not read yet
 int flash_prefill_min_cols() {
@@ -347,22 +15,6 @@ extern "C" __attribute__((visibility("default"))) void cllm_debug_set_attn_prefi
 // split-KV partials exist only on the decode path (N * (H / Hkv) <= 32 query rows per KV head, so N <= 32): a prompt needs no scratch at all
 // (it used to be sized for every N: 8.9 GB for a 2048-token -fa prefill that never touched it)
 size_t fattn_wsize(int64_t N, int64_t H, int64_t B, int64_t D) { return N > 32 ? 0 : (size_t) B * H * N * FA_MAX_SPLITS * (D + 4) * 4; }
-
-template <int D, int KVT, int VL, int MASK>
-static int fattn_launch(hipStream_t st, const fattn_args & a, int B, bool decode) {
-    const size_t lds = 64 * D * 2 + D * FA_VSTR;
-    if (decode) {
-        const dim3 grid((unsigned) a.splits, (unsigned)(a.H / a.R), (unsigned) B);
-        hipLaunchKernelGGL((k_fattn<D, KVT, VL, MASK, 4>), grid, dim3(256), lds, st, a);     // four waves stage the tile (one load latency); the wave that owns the rows computes
-        LAUNCH_CHECK();
-        if (a.splits > 1) { hipLaunchKernelGGL((k_fattn_merge<D>), dim3((unsigned) a.N, (unsigned) a.H, (unsigned) B), dim3(1024), 0, st, a); LAUNCH_CHECK(); }
-    } else {
-        const dim3 grid((unsigned)((a.N + 127) / 128), (unsigned) a.H, (unsigned) B);
-        hipLaunchKernelGGL((k_fattn<D, KVT, VL, MASK, 4>), grid, dim3(256), lds, st, a);
-        LAUNCH_CHECK();
-    }
-    return CLLM_OK;
-}
 
 // q F32 [D, N, H, B]; k [D, n_kv, Hkv, B]; v: vl 0 [D, n_kv, Hkv, B], vl 1 [n_kv(ML), D, Hkv, B] (F16); mask F16 [n_kv, N, ..] or null;
 // causal_past >= 0 (no mask tensor): position kv is visible to query n iff kv <= causal_past + n.
@@ -415,20 +67,8 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
     }
     if (vl == 1 && (v.nb[1] / 2) % 8) return CLLM_E_UNSUPPORTED;
     if (hs) return fattn_hs_launch(st, a, (int) D, ktype, mmode, (int) B, decode);
-#define FA_GO(D_, KVT_, VL_, M_) return fattn_launch<D_, KVT_, VL_, M_>(st, a, (int) B, decode)
-#define FA_MASKS(D_, KVT_, VL_) do { if (mmode == 0) FA_GO(D_, KVT_, VL_, 0); if (mmode == 1) FA_GO(D_, KVT_, VL_, 1); FA_GO(D_, KVT_, VL_, 2); } while (0)
-    if (D == 128) {
-        if (ktype == CLLM_TYPE_Q8_0) FA_MASKS(128, CLLM_TYPE_Q8_0, 0);
-        if (vl == 1) FA_MASKS(128, CLLM_TYPE_F16, 1);
-        FA_MASKS(128, CLLM_TYPE_F16, 0);
-    } else {
-        if (ktype == CLLM_TYPE_Q8_0) FA_MASKS(64, CLLM_TYPE_Q8_0, 0);
-        if (vl == 1) FA_MASKS(64, CLLM_TYPE_F16, 1);
-        FA_MASKS(64, CLLM_TYPE_F16, 0);
-    }
-#undef FA_MASKS
-#undef FA_GO
-    return CLLM_E_UNSUPPORTED;
+    if (D == 128) return fattn_dispatch<128>(st, a, ktype, vl, mmode, (int) B, decode);
+    return fattn_dispatch<64>(st, a, ktype, vl, mmode, (int) B, decode);
 }
 
 // ---- single-token attention above attn_long_threshold() cached positions inside a captured decode step (the runner's graph, the module's
@@ -485,11 +125,10 @@ int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * po
     const int tiles = (int)((ML + 63) / 64);
     int per = (tiles + max_splits - 1) / max_splits; if (per < tiles / 32) per = tiles / 32; if (per < 1) per = 1;
     a.chunk = per * 64; a.splits = (tiles + per - 1) / per;
-    const size_t lds = 64 * (size_t) hd * 2 + (size_t) hd * FA_VSTR;
     const dim3 grid((unsigned) a.splits, (unsigned) nkv, 1);
     return with_head_dim(hd, [&](auto hd_c) -> int {
         constexpr int HD = decltype(hd_c)::value;
-        hipLaunchKernelGGL((k_fattn<HD, CLLM_TYPE_F16, 1, 0, 4>), grid, dim3(256), lds, st, a);
+        hipLaunchKernelGGL((k_fattn<HD, CLLM_TYPE_F16, 1, 0>), grid, dim3(256), fa_lds_bytes<HD>(), st, a);
         LAUNCH_CHECK();
         hipLaunchKernelGGL((k_fattn_merge<HD>), dim3(1, (unsigned) nh, 1), dim3(1024), 0, st, a);
         LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-"""A plain-numpy model of the flash attention kernels (fattn.hip: k_fattn, k_fattn_merge): no GPU, no package import.
+"""A plain-numpy model of the flash attention kernels (fattn.h: k_fattn, k_fattn_merge): no GPU, no package import.
 
 It says, per OUTPUT ELEMENT, how far the kernel may be from the float64 value of what it computes, and it restates the kernel's algorithm step by step so
 that the CPU suite can show (a) that the inputs below drive the paths they claim to and (b) that the bound separates a right kernel from a wrong one.

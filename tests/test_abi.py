@@ -74,6 +74,8 @@ def _resource_usage(name):
     assert m, "csrc/Makefile: FLAGS line not found"
     arch = re.search(r"^ARCH\s*\?=\s*(\S+)", mk, re.M).group(1)
     flags = m.group(1).replace("$(ARCH)", arch).split()
+    for extra in re.findall(r"^build/%s\.o:\s*FLAGS\s*\+=\s*(.*)$" % re.escape(os.path.splitext(name)[0]), mk, re.M):      # the file's target-specific flags
+        flags += extra.split()
     assert "-ffp-contract=off" in flags and any(f.startswith("--offload-arch=") for f in flags), flags
     out = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -95,6 +97,25 @@ def test_the_row_streaming_mat_vec_kernels_do_not_spill(name, kernels):
     err = _resource_usage(name)
     spills = re.findall(r"VGPRs Spill: (\d+)", err) + re.findall(r"SGPRs Spill: (\d+)", err) + re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)
     assert len(spills) >= 3 * kernels and all(int(x) == 0 for x in spills), sorted(set(spills))
+
+
+def test_flash_attention_at_head_sizes_96_and_256_does_not_spill():
+    """k_fattn (fattn.h) at D = 256 runs one workgroup per CU, one wave per SIMD with the whole register file, and loads a tile between its two barriers instead of
+    one tile ahead: both were chosen so that nothing spills (fattn.h's D = 256 paragraph).  The twelve k_fattn of fattn_hs.hip and all four k_fattn_merge (two in
+    each file) report no spilled SGPR or VGPR and no scratch, and the six at D = 256 the occupancy of 1 the design chose"""
+    mk = open(os.path.join(ROOT, "chatllm.cpp_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^build/fattn_hs\.o:\s*FLAGS\s*\+=.*-packed-fp32-ops", mk, re.M), "csrc/Makefile: the flags of fattn_hs.o are not where _resource_usage looks for them"
+    hs = re.split(r"remark: Function Name: ", _resource_usage("fattn_hs.hip"))[1:]
+    main = [b for b in hs if re.match(r"_Z7k_fattnILi(96|256)E", b)]
+    merge = [b for b in hs if re.match(r"_Z13k_fattn_mergeILi(96|256)E", b)]
+    assert len(main) == 12 and len(merge) == 2 and len(hs) == 14, [b.split()[0] for b in hs]
+    merge += [b for b in re.split(r"remark: Function Name: ", _resource_usage("fattn.hip"))[1:] if re.match(r"_Z13k_fattn_mergeILi(64|128)E", b)]
+    assert len(merge) == 4, [b.split()[0] for b in merge]
+    for b in main + merge:
+        fig = {k: int(v) for k, v in re.findall(r"(SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", b)}
+        assert fig["SGPRs Spill"] == 0 and fig["VGPRs Spill"] == 0 and fig["ScratchSize [bytes/lane]"] == 0, b.split()[0] + " " + str(fig)
+        if b.startswith("_Z7k_fattnILi256E"):
+            assert fig["Occupancy [waves/SIMD]"] == 1, b.split()[0] + " " + str(fig)
 
 
 def test_the_decode_mat_vec_kernels_use_no_scratch():

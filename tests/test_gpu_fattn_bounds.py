@@ -1,4 +1,4 @@
-"""GPU: flash attention (fattn.hip: k_fattn, k_fattn_merge) element by element against float64, on score profiles that drive the lazy rescale, p > 1,
+"""GPU: flash attention (fattn.h: k_fattn, k_fattn_merge) element by element against float64, on score profiles that drive the lazy rescale, p > 1,
 fp16-subnormal p, merge weights far from 1 and the masking edges.
 
 tests/test_gpu_fattn.py judges the kernel by max |got - want| / max |want| on Gaussian q and k, where m_run moves once per row and every split has about the

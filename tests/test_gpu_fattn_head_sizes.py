@@ -1,4 +1,4 @@
-"""GPU: flash attention at head sizes 96 and 256 (fattn_hs.hip: k_fattn_hs, with fattn.h's k_fattn_merge) element by element against float64.
+"""GPU: flash attention at head sizes 96 and 256 (fattn.h: k_fattn and k_fattn_merge, as fattn_hs.hip instantiates them) element by element against float64.
 
 Operands, float64 reference and per-element bound come from tests/fattn_model.py (the bound does not depend on D); the call and the three assertions are
 those of tests/test_gpu_fattn_bounds.py.  The cases are the smallest shapes that reach each path: decode with packed GQA rows, 5 splits and a 44-position

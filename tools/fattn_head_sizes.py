@@ -1,4 +1,4 @@
-"""flash attention at head sizes 96 / 128 / 256 at equal H * D = 6144 (equal Q.K and P.V FLOPs): prefill 4096 x 4096 with a causal mask tensor, decode
+"""flash attention (k_fattn, fattn.h) at head sizes 96 / 128 / 256 at equal H * D = 6144 (equal Q.K and P.V FLOPs): prefill 4096 x 4096 with a causal mask tensor, decode
 1 x 4096 cached positions; F16 and Q8_0.  Device events, 3 warm-up launches, median of 20 timed windows (decode: 10 launches per window)."""
 import ctypes as C
 import os
