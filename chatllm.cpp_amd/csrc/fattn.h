@@ -1,6 +1,6 @@
 // fattn.h -- the flash attention kernel, stated once for every head size: GGML_OP_FLASH_ATTN_EXT and the same tiled kernel behind the prefill attention
 // block and the long-context decode step.  The score matrix never leaves the CU.  fattn.hip instantiates head sizes 64 / 128 and holds the entry
-// points; fattn_hs.hip instantiates 96 / 256.
+// points; fattn_hs.hip instantiates 96 / 256, fattn_pad.hip 112.
 //
 //   out[:, h, n] = sum_kv softmax_kv(scale * K[kv, h/r] . Q[n, h] + mask[kv, n]) * V[kv, h/r]
 //   ggml_compute_forward_flash_attn_ext_f16 (ggml-cpu/ops.cpp:8114-8344 one query at a time, :8346-8640 tiled, :8642-8710 the
@@ -27,7 +27,27 @@
 // (m, l, O) are merged by k_fattn_merge.
 //
 // What depends on the head size is stated once each: the K tile's LDS layout (fa_k_layout), the tile-ahead prefetch and the occupancy
-// (fa_tile_ahead, fa_min_blocks), the V^T-cache form (fa_has_vt), the grouping of the Q conversion (fa_q_group) and the K staging's guard (fa_k_guard).
+// (fa_tile_ahead, fa_min_blocks), the V^T-cache form (fa_has_vt), the grouping of the Q conversion (fa_q_group), the K staging's guard (fa_k_guard)
+// and the feature rows of the P.V product (fa_dp).
+//
+// D = 112, and with it every D % 32 == 16; the figures below are given for 80 / 112, but 80 is NOT instantiated (tests/test_gpu_fattn.py holds it as the
+//   head size the entry declines).  F16 rows only: a Q8_0 row needs D % 32 == 0, and the host gives such a head size an F16 cache.  The two products
+//   stop sharing a block count.  S^T contracts over D in KS = 5 / 7 exact steps of 16, nothing padded.  O^T has D feature ROWS, and an MFMA's A operand has 32: the V^T tile
+//   has DP = fa_dp<D>() = 96 / 128 rows, NB = DP / 32 = 3 / 4 blocks.  Row r of A reaches row r of the result and no other, so the pad rows D .. DP - 1
+//   of the V^T tile are never written (no zeroing pass, no staging: whatever the LDS holds there, NaN patterns included, ends in accumulator
+//   registers that are rescaled with the rest and never stored) and the epilogue skips the f32x4 groups at dv >= D (32 i + 8 g + 4 hi with
+//   D % 16 == 0: a whole group is in or out, at compile time).  The pad rows are ALLOCATED, not aliased onto the K tile or the live V^T rows: an
+//   alias would save 2176 B where two workgroups of 24320 / 32768 B are far from a CU's 160 KB, and nothing else (the pad rows are read either
+//   way).  Price: (2 KS + 4 NB) / (2 KS + 4 D / 32) = 22 / 20 = 1.10 MFMA slots per useful one at 80, 30 / 28 = 1.07 at 112.
+//   NOT built: the 16-row tail on v_mfma_f32_16x16x32_f16 (4 of them, 8 passes each, instead of 4 x 16 passes: 32 of a tile's 352 / 480 passes, 9 % /
+//   7 %).  Its B operand wants 16 queries x 4 lane rows of 8 positions; the lane pair holds 32 queries x 2.  Per tile that is 8 v_permlane16_swap
+//   (each pair of P fragments, 4 registers) behind the exp2 and in front of the MFMAs, 8 more live registers, and a result whose query is lane % 16:
+//   alpha, and 1 / l in the epilogue, live per lane pair (query = lane % 32), so every rescale would move them across lanes as well.  Measured
+//   (profiles/fattn_head_size_112.txt): what separates the head sizes at equal H D is the per-tile work outside the MFMAs, and the tail adds to it.
+//   K rows are 2 D + 16 = 176 / 240 bytes, 11 / 15 chunks: odd, fa_k_layout's argument holds.  64 CPR = 640 / 896 K chunks do not divide by 256
+//   threads: NKC rounds up to 3 / 4 and the surplus threads (128) load row 0 of the tile again and store nothing (fa_k_guard).  V units: 160 / 224
+//   for 256 threads, as at 96.  Q: all KS fragments as one group (fa_q_group must divide KS, and 5 and 7 are prime).  Merge: G = 12 / 9 groups and
+//   a remainder of 64 / 16 threads; partial rows of D + 4 floats are 336 / 464 bytes, so the f32x4 partial stores stay aligned.
 //
 // D = 96: KS = 6, NB = 3: 48 + 24 + 32 registers of O / Q / S, two workgroups per CU; LDS 64 * 208 + 96 * 136 = 26368 B.  K staging is three
 //   chunks per thread exactly; the V^T staging has 16 * 12 = 192 units of 4 positions x 8 features for 256 threads: the last wave loads a duplicate
@@ -98,12 +118,15 @@ __device__ __forceinline__ float fa_pair_sum(float x) {
 template <int D> struct fa_k_layout {
     static constexpr int CPR = D / 8;
     static constexpr bool swizzled = D == 64 || D == 128;
-    static constexpr int row_bytes = swizzled ? 2 * D : 2 * D + 16;
+    static constexpr int row_bytes = swizzled ? 2 * D : 2 * D + 16;      // 112: 240 (15 chunks)
     static_assert(swizzled || (CPR + 1) % 2 == 1, "an odd K row stride in chunks");
     static __device__ __forceinline__ char * chunk(char * tile, int row, int col) { return tile + row * row_bytes + ((swizzled ? col ^ (row & (CPR - 1)) : col) << 4); }
 };
+// Feature rows of the V^T tile and of O^T: D rounded up to the 32 rows of an MFMA's A operand (80 -> 96, 112 -> 128); rows D .. fa_dp - 1 are never
+// written and never stored (the header's D = 112 paragraph)
+template <int D> constexpr int fa_dp() { return (D + 31) & ~31; }
 // LDS of one workgroup: the K tile, then the V^T tile
-template <int D> constexpr int fa_lds_bytes() { return 64 * fa_k_layout<D>::row_bytes + D * FA_VSTR; }
+template <int D> constexpr int fa_lds_bytes() { return 64 * fa_k_layout<D>::row_bytes + fa_dp<D>() * FA_VSTR; }
 // Up to 128 the next tile's K / V rows are loaded into registers one tile ahead (the loads fly under the MFMA work of the current tile) and two
 // workgroups share a CU.  At 256 those staging registers do not fit beside O, Q and S (the header's D = 256 paragraph): a tile's rows are loaded
 // and stored between its two barriers, and one workgroup per CU gives each wave the full 512-register file.
@@ -114,20 +137,21 @@ template <int D> constexpr int fa_min_blocks() { return D > 128 ? 1 : 2; }
 template <int D> constexpr bool fa_has_vt() { return D == 64 || D == 128; }
 // Q fragments loaded, converted and rounded to fp16 as one group (the values do not depend on it: a Q8_0 block is two fragments).  Up to 128 all of
 // them at once, every load issued before the first conversion; at 96 and 256 block by block, so a block's floats are dead before the next block's
-// arrive (at 256 the whole row as floats would be 64 registers beside the 128 of O).
-template <int D> constexpr int fa_q_group() { return D == 64 || D == 128 ? D / 16 : 2; }
-// The 64 CPR chunks of a K tile divide evenly over the 256 threads at all four head sizes, so no thread is without a chunk and a guard on the K
+// arrive (at 256 the whole row as floats would be 64 registers beside the 128 of O).  112 (80): KS is prime and the rows are F16, all at once.
+template <int D> constexpr int fa_q_group() { return D == 64 || D == 128 || D % 32 ? D / 16 : 2; }
+// The 64 CPR chunks of a K tile divide evenly over the 256 threads at 64 / 96 / 128 / 256, so no thread is without a chunk and a guard on the K
 // staging (row 0 instead of a row past the tile, no store) never acts.  The compiler does not drop it, though: at 96 / 256 it costs a select per
 // chunk, on the critical path at 256 where a tile's loads sit between its two barriers (decode D = 256 F16: 19.7 against 19.3 us), so those sizes
 // have none.  64 / 128 keep theirs: without it each of their kernels comes out 6 .. 20 instructions different from the code the runner's prefill
-// and long-context paths were measured with, for nothing that has been measured.
-template <int D> constexpr bool fa_k_guard() { return D == 64 || D == 128; }
+// and long-context paths were measured with, for nothing that has been measured.  112 (896 chunks; 80: 640) needs it: there it acts.
+template <int D> constexpr bool fa_k_guard() { return D == 64 || D == 128 || (64 * (D / 8)) % 256 != 0; }
 
 template <int D, int KVT, int VL, int MASK>
 __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_args a) {
     using KL = fa_k_layout<D>;
-    constexpr int NT = 256, BQ = 128, KS = D / 16, NB = D / 32, CPR = D / 8, QG = fa_q_group<D>();
-    static_assert(D % 32 == 0, "Q8_0 blocks per row");
+    constexpr int NT = 256, BQ = 128, KS = D / 16, DP = fa_dp<D>(), NB = DP / 32, CPR = D / 8, QG = fa_q_group<D>();
+    static_assert(D % 16 == 0 && KS % QG == 0, "whole S^T steps, whole Q groups");
+    static_assert(KVT != CLLM_TYPE_Q8_0 || (D % 32 == 0 && QG % 2 == 0), "Q8_0 blocks per row, two fragments per block");
     static_assert(VL == 0 || (fa_has_vt<D>() && KVT == CLLM_TYPE_F16), "V^T rows: F16 at 64 / 128");
     extern __shared__ __attribute__((aligned(16))) char fa_smem[];
     char * Kl = fa_smem, * Vl = fa_smem + 64 * KL::row_bytes;
@@ -198,10 +222,10 @@ __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_a
     //      transposition; between the two barriers of a tile).  Q8_0 rows keep their raw 16-bit pieces in the registers (34-byte blocks: 2-byte
     //      alignment) and are dequantized on the way into LDS.
     //      A thread count that does not divide the chunk count leaves the last threads a duplicate load (in bounds) and no store: the V units at 64 and 96
-    //      (128 and 192 of them for 256 threads).  The K chunks divide evenly at all four sizes: fa_k_guard.
-    static_assert((64 * CPR) % NT == 0 && (VL == 0 || (D * 8) % NT == 0), "K (and V^T) chunks: every thread has one");
+    //      (128 and 192 of them for 256 threads), and at 112 both the V units (224) and the K chunks (896: fa_k_guard).
+    static_assert(((64 * CPR) % NT == 0 || fa_k_guard<D>()) && (VL == 0 || (D * 8) % NT == 0), "K chunks: every thread has one, or the guard; V^T chunks: every thread has one");
     constexpr bool Q8 = KVT == CLLM_TYPE_Q8_0;
-    constexpr int NKC = (64 * CPR + NT - 1) / NT;                     // K chunks (8 elements) per thread: 2 | 3 | 4 | 8
+    constexpr int NKC = (64 * CPR + NT - 1) / NT;                     // K chunks (8 elements) per thread: 2 | 3 | 4 | 8 (112: 4, the last one for half the threads)
     constexpr int NVU = VL == 1 ? (D * 8 + NT - 1) / NT : (16 * CPR + NT - 1) / NT;      // V^T chunks (VL 1) / 4-row x 8-element units (VL 0) per thread
     struct raw8 { uint32_t h[4]; uint32_t d; };                      // Q8_0: four 16-bit pieces of 8 quants + the block scale
     u32x4 kreg[Q8 ? 1 : NKC]; raw8 kraw[Q8 ? NKC : 1];
@@ -259,7 +283,7 @@ __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_a
 #pragma unroll
         for (int t = 0; t < NKC; t++) {
             const int c = tid + t * NT, row = c / CPR, col = c % CPR;
-            *(u32x4 *) KL::chunk(Kl, row, col) = Q8 ? q8_cvt(kraw[Q8 ? t : 0]) : kreg[Q8 ? 0 : t];
+            if ((64 * CPR) % NT == 0 || c < 64 * CPR) *(u32x4 *) KL::chunk(Kl, row, col) = Q8 ? q8_cvt(kraw[Q8 ? t : 0]) : kreg[Q8 ? 0 : t];
         }
         if constexpr (fa_has_vt<D>()) if (VL == 1) {
 #pragma unroll
@@ -398,7 +422,7 @@ __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_a
             for (int r = 0; r < 16; r++) { const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][r], a.sc2, -msafe)); s[j][r] = p; psum += p; }
         l_run += psum;
 
-        // ---- O^T += V^T . P^T: 4 NB MFMAs, V^T fragments read FA_PD ahead
+        // ---- O^T += V^T . P^T: 4 NB MFMAs, V^T fragments read FA_PD ahead (112: the last block's rows D .. DP - 1 are whatever the LDS holds)
         {
             half8 pb[4];
 #pragma unroll
@@ -424,7 +448,7 @@ __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_a
         }
     }
 
-    // ---- epilogue: lane holds O^T[dv = 32 i + crow(r, hi), q = l31]: groups of 4 consecutive dv
+    // ---- epilogue: lane holds O^T[dv = 32 i + crow(r, hi), q = l31]: groups of 4 consecutive dv; the groups of the pad rows (dv >= D) are not stored
     const float l_tot = fa_pair_sum(l_run);
     if (!rvalid) return;
     if (a.splits == 1) {
@@ -434,21 +458,21 @@ __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_a
         for (int i = 0; i < NB; i++)
 #pragma unroll
             for (int g = 0; g < 4; g++)
-                *(f32x4 *)(dp + (32 * i + 8 * g + 4 * hi) * 4) = f32x4{o[i][4 * g] * inv, o[i][4 * g + 1] * inv, o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv};
+                if (DP == D || 32 * i + 8 * g < D) *(f32x4 *)(dp + (32 * i + 8 * g + 4 * hi) * 4) = f32x4{o[i][4 * g] * inv, o[i][4 * g + 1] * inv, o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv};
     } else {
         float * pp = a.part + ((((int64_t) b * a.H + h) * a.N + n) * a.splits + split) * (D + 4);
 #pragma unroll
         for (int i = 0; i < NB; i++)
 #pragma unroll
             for (int g = 0; g < 4; g++)
-                *(f32x4 *)(pp + 32 * i + 8 * g + 4 * hi) = f32x4{o[i][4 * g], o[i][4 * g + 1], o[i][4 * g + 2], o[i][4 * g + 3]};
+                if (DP == D || 32 * i + 8 * g < D) *(f32x4 *)(pp + 32 * i + 8 * g + 4 * hi) = f32x4{o[i][4 * g], o[i][4 * g + 1], o[i][4 * g + 2], o[i][4 * g + 3]};
         if (hi == 0) { pp[D] = m_run; pp[D + 1] = l_tot; }
     }
 }
 
 // merge the split-KV partials of one (b, h, n) (ggml_flash_attn_ext_reduce_partials, ops.cpp:8642-8710): 1024 threads = D output elements x
 // G = 1024 / D interleaved groups of splits, so that the loads of different splits are independent and coalesced.  D = 96: G = 10, and the last
-// 64 threads (a partial eleventh group) take part in the two reductions over the splits only
+// 64 threads (a partial eleventh group) take part in the two reductions over the splits only; likewise 112 (G = 9, 16 threads)
 template <int D>
 __global__ void __launch_bounds__(1024) k_fattn_merge(const fattn_args a) {
     constexpr int G = 1024 / D;
@@ -506,16 +530,20 @@ static int fattn_go_mask(hipStream_t st, const fattn_args & a, int mmode, int B,
     if (mmode == 1) return fattn_go<D, KVT, VL, 1>(st, a, B, decode);
     return fattn_go<D, KVT, VL, 2>(st, a, B, decode);
 }
-// every instantiation of one head size: ktype F16 | Q8_0 (launch_fattn has checked it), vl 1 with F16 where fa_has_vt, mmode 0 none | 1 causal | 2 tensor
+// every instantiation of one head size: ktype F16 | Q8_0 (launch_fattn has checked it; Q8_0 where D % 32 == 0), vl 1 with F16 where fa_has_vt, mmode 0 none | 1 causal | 2 tensor
 template <int D>
 static int fattn_dispatch(hipStream_t st, const fattn_args & a, int ktype, int vl, int mmode, int B, bool decode) {
     if (vl == 1) {
         if constexpr (fa_has_vt<D>()) { if (ktype == CLLM_TYPE_F16) return fattn_go_mask<D, CLLM_TYPE_F16, 1>(st, a, mmode, B, decode); }
         return CLLM_E_UNSUPPORTED;
     }
-    if (ktype == CLLM_TYPE_Q8_0) return fattn_go_mask<D, CLLM_TYPE_Q8_0, 0>(st, a, mmode, B, decode);
+    if (ktype == CLLM_TYPE_Q8_0) {                                     // a Q8_0 row is whole blocks of 32: not instantiated at 112
+        if constexpr (D % 32 == 0) return fattn_go_mask<D, CLLM_TYPE_Q8_0, 0>(st, a, mmode, B, decode);
+        return CLLM_E_UNSUPPORTED;
+    }
     return fattn_go_mask<D, CLLM_TYPE_F16, 0>(st, a, mmode, B, decode);
 }
 
-// fattn_hs.hip: the head sizes 96 / 256 (V rows by position only)
+// fattn_hs.hip: the head sizes 96 / 256; fattn_pad.hip: 112, F16 rows (V rows by position only)
 int fattn_hs_launch(hipStream_t st, const fattn_args & a, int D, int ktype, int mmode, int B, bool decode);
+int fattn_pad_launch(hipStream_t st, const fattn_args & a, int D, int ktype, int mmode, int B, bool decode);

@@ -1,5 +1,5 @@
 // fattn.hip -- flash attention's entry points (launch_fattn: validation and the split plan for every head size; launch_attn_long_flash: the
-// long-context decode step) and the instantiations of k_fattn (fattn.h) at head sizes 64 and 128; 96 and 256 are fattn_hs.hip.
+// long-context decode step) and the instantiations of k_fattn (fattn.h) at head sizes 64 and 128; 96 and 256 are fattn_hs.hip, 112 is fattn_pad.hip.
 #include "fattn.h"
 
 static int g_flash_min = -1;             // -1: not read yet
@@ -23,7 +23,8 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
                  char * dst, int64_t nbn, int64_t nbh, int64_t nbb, float scale, void * wdata, size_t wsize) {
     const int64_t D = q.ne[0], N = q.ne[1], H = q.ne[2], B = q.ne[3], n_kv = k.ne[1], Hkv = k.ne[2];
     const bool hs = D == 96 || D == 256;                   // fattn_hs.hip (V rows by position only)
-    if (D != 64 && D != 128 && !(hs && vl == 0)) return CLLM_E_UNSUPPORTED;
+    const bool pad = D == 112;                             // fattn_pad.hip (V rows by position only, F16)
+    if (D != 64 && D != 128 && !((hs || pad) && vl == 0)) return CLLM_E_UNSUPPORTED;
     if (k.ne[0] != D || (vl == 0 ? v.ne[0] != D || v.ne[1] != n_kv : v.ne[1] != D || v.ne[0] < n_kv) || v.ne[2] != Hkv || Hkv <= 0 || H % Hkv || k.ne[3] != B || v.ne[3] != B) return CLLM_E_UNSUPPORTED;
     if (ktype != CLLM_TYPE_F16 && ktype != CLLM_TYPE_Q8_0) return CLLM_E_UNSUPPORTED;
     if (vl == 1 && ktype != CLLM_TYPE_F16) return CLLM_E_UNSUPPORTED;
@@ -67,6 +68,7 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
     }
     if (vl == 1 && (v.nb[1] / 2) % 8) return CLLM_E_UNSUPPORTED;
     if (hs) return fattn_hs_launch(st, a, (int) D, ktype, mmode, (int) B, decode);
+    if (pad) return fattn_pad_launch(st, a, (int) D, ktype, mmode, (int) B, decode);
     if (D == 128) return fattn_dispatch<128>(st, a, ktype, vl, mmode, (int) B, decode);
     return fattn_dispatch<64>(st, a, ktype, vl, mmode, (int) B, decode);
 }

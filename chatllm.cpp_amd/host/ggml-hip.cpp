@@ -433,7 +433,7 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
             if (!a || !b || !v || op->src[4] || max_bias != 0.0f || softcap != 0.0f || op->type != GGML_TYPE_F32 || a->type != GGML_TYPE_F32 || a->nb[0] != 4) return false;
             if (b->type != v->type || (b->type != GGML_TYPE_F16 && b->type != GGML_TYPE_Q8_0) || b->nb[0] != ggml_type_size(b->type) || v->nb[0] != ggml_type_size(v->type)) return false;
             const int64_t D = a->ne[0];
-            if ((D != 64 && D != 96 && D != 128 && D != 256) || b->ne[0] != D || v->ne[0] != D || v->ne[1] != b->ne[1] || b->ne[2] <= 0 || a->ne[2] % b->ne[2] || v->ne[2] != b->ne[2] || a->ne[3] != b->ne[3] || a->ne[3] != v->ne[3]) return false;
+            if ((D != 64 && D != 96 && D != 112 && D != 128 && D != 256) || (D % 32 && b->type != GGML_TYPE_F16) || b->ne[0] != D || v->ne[0] != D || v->ne[1] != b->ne[1] || b->ne[2] <= 0 || a->ne[2] % b->ne[2] || v->ne[2] != b->ne[2] || a->ne[3] != b->ne[3] || a->ne[3] != v->ne[3]) return false;
             if (a->nb[1] % 16 || a->nb[2] % 16 || a->nb[3] % 16 || !ggml_is_contiguous(op)) return false;
             if (b->type == GGML_TYPE_F16 && (b->nb[1] % 16 || b->nb[2] % 16 || b->nb[3] % 16 || v->nb[1] % 16 || v->nb[2] % 16 || v->nb[3] % 16)) return false;
             if (m && (m->type != GGML_TYPE_F16 || !ggml_is_contiguous(m) || m->ne[0] < b->ne[1] || m->ne[1] < a->ne[1])) return false;

@@ -1,5 +1,9 @@
 """flash attention (k_fattn, fattn.h) at head sizes 96 / 128 / 256 at equal H * D = 6144 (equal Q.K and P.V FLOPs): prefill 4096 x 4096 with a causal mask tensor, decode
-1 x 4096 cached positions; F16 and Q8_0.  Device events, 3 warm-up launches, median of 20 timed windows (decode: 10 launches per window)."""
+1 x 4096 cached positions; F16 and Q8_0.  Device events, 3 warm-up launches, median of 20 timed windows (decode: 10 launches per window).
+
+Then (alone with the argument `112`) the head size 112 (F16 rows only) beside the kernel whose P.V work it issues, 128, at equal H * D = 7168 (H 64 | 56),
+and 96 at 5760 (H 60) for the line through the two unpadded kernels; H % 4 == 0, three rounds, the sizes alternating inside a round.  The rates count
+useful FLOPs (D, not the padded feature count)."""
 import ctypes as C
 import os
 import sys
@@ -46,8 +50,8 @@ def kv(r, kv_t, D, n_kv, Hkv, s):
     return T.from_numpy(FM.q8_0_quantize(x).reshape(-1), gpu.Q8_0, [D, n_kv, Hkv]), D // 32 * 34
 
 
-def run(D, kv_t, N, n_kv, mask):
-    H = 6144 // D
+def run(D, kv_t, N, n_kv, mask, HD=6144):
+    H = HD // D
     Hkv = H // 4
     r = np.random.default_rng(D + N)
     q = T.from_numpy(r.standard_normal((H, N, D)).astype(np.float32), gpu.F32, [D, N, H])
@@ -70,9 +74,15 @@ N = 4096
 m = np.zeros((N, N), np.float16)
 m[np.triu_indices(N, 1)] = -np.inf
 dm = T.from_numpy(m, gpu.F16, [N, N])
-for kv_t in (FM.F16, FM.Q8_0):
-    for D in (128, 96, 256):
-        run(D, kv_t, N, N, dm)
-for kv_t in (FM.F16, FM.Q8_0):
-    for D in (128, 96, 256):
-        run(D, kv_t, 1, N, None)
+if sys.argv[1:] != ["112"]:
+    for kv_t in (FM.F16, FM.Q8_0):
+        for D in (128, 96, 256):
+            run(D, kv_t, N, N, dm)
+    for kv_t in (FM.F16, FM.Q8_0):
+        for D in (128, 96, 256):
+            run(D, kv_t, 1, N, None)
+PAIRS = ((96, 5760), (112, 7168), (128, 7168))
+for n, mask in ((N, dm), (1, None)):
+    for _ in range(3):
+        for D, HD in PAIRS:
+            run(D, FM.F16, n, N, mask, HD)
