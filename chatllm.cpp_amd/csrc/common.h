@@ -848,7 +848,7 @@ int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * po
 int flash_prefill_min_cols();          // query rows from which the eager attention block runs as the flash kernel (CLLM_FLASH_PREFILL=0: never)
 size_t fattn_wsize(int64_t N, int64_t H, int64_t B, int64_t D);
 int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, const tview & v, int vl, const tview * mask, int causal_past,
-                 char * dst, int64_t nbn, int64_t nbh, int64_t nbb, float scale, void * wdata, size_t wsize);
+                 char * dst, int64_t nbn, int64_t nbh, int64_t nbb, float scale, float cap, void * wdata, size_t wsize);      // cap: logit soft-cap, 0 = none
 int launch_gemv_decode_id_combine(hipStream_t st, int wtype, const void * W, size_t w_expert_bytes, int64_t K, int64_t nrows, const float * px, int64_t px_slot_stride,
                                   const int32_t * ids, const float * probs, const float * resid, float * dst);
 int launch_quantize_act_silu2(hipStream_t st, int kind, const tview & g, const tview & u, void * act, size_t act_stride);

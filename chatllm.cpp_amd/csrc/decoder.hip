@@ -421,7 +421,7 @@ static int forward_general(cllm_llama * m, int qlen, int n_past) {
             if (qlen >= flash_prefill_min_cols() && prefill_attn_mode() != 1) {     // fast mode, the tolerance tier (as the MFMA mat-muls below): one flash kernel, the scores never reach HBM
                 tview vt = tv(&Vv); vt.ne[0] = ML;
                 frc = launch_fattn((hipStream_t) st, tv(&Qv), tv(&Kv), CLLM_TYPE_F16, vt, 1, nullptr, n_past, (char *) m->att, (int64_t) QD * 4, (int64_t) hd * 4,
-                                   (int64_t) QD * 4 * qlen, 1.0f / sqrtf((float) hd), nullptr, 0);
+                                   (int64_t) QD * 4 * qlen, 1.0f / sqrtf((float) hd), 0.0f, nullptr, 0);
                 if (frc != CLLM_OK && frc != CLLM_E_UNSUPPORTED) return frc;
             }
             if (frc == CLLM_E_UNSUPPORTED) {

@@ -1,6 +1,6 @@
 // fattn.h -- the flash attention kernel, stated once for every head size: GGML_OP_FLASH_ATTN_EXT and the same tiled kernel behind the prefill attention
 // block and the long-context decode step.  The score matrix never leaves the CU.  fattn.hip instantiates head sizes 64 / 128 and holds the entry
-// points; fattn_hs.hip instantiates 96 / 256, fattn_pad.hip 112.
+// points; fattn_hs.hip instantiates 96 / 256, fattn_pad.hip 112, fattn_cap.hip the logit soft-cap (CAP) at 128 / 256.
 //
 //   out[:, h, n] = sum_kv softmax_kv(scale * K[kv, h/r] . Q[n, h] + mask[kv, n]) * V[kv, h/r]
 //   ggml_compute_forward_flash_attn_ext_f16 (ggml-cpu/ops.cpp:8114-8344 one query at a time, :8346-8640 tiled, :8642-8710 the
@@ -64,6 +64,16 @@
 //   with the K and V^T tiles one workgroup per CU again, and two LDS reads per S MFMA); a 32-position KV tile (halves S and staging, not O, and
 //   the soft-max would rescale per 32 positions, which term (c) does not count); O's dv blocks split over two waves sharing one score tile (fits
 //   256 registers, needs P and the row statistics exchanged through LDS every tile) -- the candidate for closing the gap.
+//
+// CAP (logit_softcap != 0; fattn_cap.hip: D = 128 / 256, F16 / Q8_0 rows by position, no mask or a mask tensor):
+//   s = cap tanh(scale / cap K[kv] . Q[n]) + mask[kv, n]   (ggml_compute_forward_flash_attn_ext_f16: scale /= cap, tanh, * cap, + mask)
+//   Between the two MFMA blocks each of the lane's 32 score registers becomes t = fa_tanh(s a.cap_in), cap_in = scale / cap, and the host sets
+//   sc2 = cap log2(e) instead of scale log2(e).  Everything downstream already speaks in "raw score times sc2" and so works in units of t unchanged:
+//   mask_mul = log2(e) / sc2 is 1 / cap (the mask joins t as mask / cap and leaves the exponent as mask log2(e)), the -inf fills, the lazy maximum
+//   (m_run, FA_TAU: log2 domain), exp2(fma(t, sc2, -m)), the split-KV partials and the merge.  A row of a ragged tile beyond kv_hi is a re-read of
+//   the last row: a finite tanh, then filled with -inf like any score.  The tanh stands outside the staging lambdas (what they capture moves the
+//   prologue's schedule); without CAP it is not there, and the kernels of the three other files are the parent's instruction for instruction
+//   (profiles/fattn_softcap.txt).
 #pragma once
 #include "attn_token.h"      // k_slot, v_slot: the cache layouts k_rope_kv_prep writes
 #include <stdlib.h>
@@ -90,7 +100,8 @@ struct fattn_args {
     float * part;                                           // splits > 1: [B][H][N][splits][D + 4] = O (unnormalized), m (log2 domain), l
     int N, H, Hkv, R, n_kv, n_past, splits, chunk;
     const int32_t * n_kv_dev;                               // decode inside a captured step: the number of cached positions is *n_kv_dev + 1 (n_kv: the upper bound)
-    float sc2;                                              // scale * log2(e)
+    float sc2;                                              // scale * log2(e); CAP: cap * log2(e)
+    float cap_in;                                           // CAP: scale / cap, the factor of the raw score under the tanh (last: no other field moves)
 };
 
 __device__ __forceinline__ int fa_crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -146,7 +157,16 @@ template <int D> constexpr int fa_q_group() { return D == 64 || D == 128 || D % 
 // and long-context paths were measured with, for nothing that has been measured.  112 (896 chunks; 80: 640) needs it: there it acts.
 template <int D> constexpr bool fa_k_guard() { return D == 64 || D == 128 || (64 * (D / 8)) % 256 != 0; }
 
-template <int D, int KVT, int VL, int MASK>
+// CAP: tanh(u) = 1 - 2 / (1 + e^(2u)) on the hardware's exp2 and rcp: no branch, one temporary, and no libm call frame (at D = 256 the kernel has
+// 440 .. 509 registers).  e^(2u) overflows to inf for u > 44 (rcp -> 0, the result exactly 1) and underflows to 0 for u < -52 (rcp(1) = 1, exactly
+// -1).  exp2 and rcp are good to 1 ulp each and the sum and the difference round once each: a few 1e-7 ABSOLUTE, also around u = 0 where the
+// difference cancels.  The soft-max multiplies it by sc2 = cap log2(e) (72 at cap 50) in the exponent: about 1e-5 relative on a probability, two
+// orders below the fp16 rounding of P (4.9e-4) that the tolerance tier is made of.
+__device__ __forceinline__ float fa_tanh(float u) {
+    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u * (2.0f * FA_LOG2E)));
+}
+
+template <int D, int KVT, int VL, int MASK, bool CAP = false>
 __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_args a) {
     using KL = fa_k_layout<D>;
     constexpr int NT = 256, BQ = 128, KS = D / 16, DP = fa_dp<D>(), NB = DP / 32, CPR = D / 8, QG = fa_q_group<D>();
@@ -379,6 +399,13 @@ __global__ void __launch_bounds__(256, fa_min_blocks<D>()) k_fattn(const fattn_a
             }
             __builtin_amdgcn_sched_barrier(0);
         }
+        // ---- logit soft-cap: the raw score becomes tanh(s scale / cap), in (-1, 1); from here on sc2 = cap log2(e) is its scale (the header's CAP paragraph)
+        if (CAP) {
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) s[j][r] = fa_tanh(s[j][r] * a.cap_in);
+        }
 
         // ---- online soft-max (base 2) of the row held by this lane pair.  The exponent reference m_run follows the running maximum lazily:
         //      it moves (and O, l are rescaled) only when a tile's maximum exceeds it by more than FA_TAU, so p <= 2^FA_TAU (fp16 holds it with the
@@ -513,13 +540,13 @@ __global__ void __launch_bounds__(1024) k_fattn_merge(const fattn_args a) {
 
 // ---- launch (a, decode: as launch_fattn planned them).  decode: one workgroup per (split, KV group, batch), four waves stage the tile (one load
 //      latency), the wave that owns the packed rows computes, then the merge; prefill: 128 query rows per workgroup (R = 1)
-template <int D, int KVT, int VL, int MASK>
+template <int D, int KVT, int VL, int MASK, bool CAP = false>
 static int fattn_go(hipStream_t st, const fattn_args & a, int B, bool decode) {
     constexpr int lds = fa_lds_bytes<D>();
     static_assert(lds <= 160 * 1024, "one CU's LDS");
-    if (lds > 64 * 1024) { static uint64_t flag = 0; if (int rc = lds_opt_in(k_fattn<D, KVT, VL, MASK>, flag, lds)) return rc; }
+    if (lds > 64 * 1024) { static uint64_t flag = 0; if (int rc = lds_opt_in(k_fattn<D, KVT, VL, MASK, CAP>, flag, lds)) return rc; }
     const dim3 grid(decode ? (unsigned) a.splits : (unsigned)((a.N + 127) / 128), (unsigned)(a.H / a.R), (unsigned) B);
-    hipLaunchKernelGGL((k_fattn<D, KVT, VL, MASK>), grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL((k_fattn<D, KVT, VL, MASK, CAP>), grid, dim3(256), lds, st, a);
     LAUNCH_CHECK();
     if (a.splits > 1) { hipLaunchKernelGGL((k_fattn_merge<D>), dim3((unsigned) a.N, (unsigned) a.H, (unsigned) B), dim3(1024), 0, st, a); LAUNCH_CHECK(); }
     return CLLM_OK;
@@ -544,6 +571,8 @@ static int fattn_dispatch(hipStream_t st, const fattn_args & a, int ktype, int v
     return fattn_go_mask<D, CLLM_TYPE_F16, 0>(st, a, mmode, B, decode);
 }
 
-// fattn_hs.hip: the head sizes 96 / 256; fattn_pad.hip: 112, F16 rows (V rows by position only)
+// fattn_hs.hip: the head sizes 96 / 256; fattn_pad.hip: 112, F16 rows (V rows by position only); fattn_cap.hip: the logit soft-cap at 128 / 256
+// (V rows by position, mmode 0 | 2)
 int fattn_hs_launch(hipStream_t st, const fattn_args & a, int D, int ktype, int mmode, int B, bool decode);
 int fattn_pad_launch(hipStream_t st, const fattn_args & a, int D, int ktype, int mmode, int B, bool decode);
+int fattn_cap_launch(hipStream_t st, const fattn_args & a, int D, int ktype, int mmode, int B, bool decode);

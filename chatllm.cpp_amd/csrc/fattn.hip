@@ -1,5 +1,6 @@
 // fattn.hip -- flash attention's entry points (launch_fattn: validation and the split plan for every head size; launch_attn_long_flash: the
-// long-context decode step) and the instantiations of k_fattn (fattn.h) at head sizes 64 and 128; 96 and 256 are fattn_hs.hip, 112 is fattn_pad.hip.
+// long-context decode step) and the instantiations of k_fattn (fattn.h) at head sizes 64 and 128; 96 and 256 are fattn_hs.hip, 112 is fattn_pad.hip,
+// the logit soft-cap at 128 and 256 is fattn_cap.hip.
 #include "fattn.h"
 
 static int g_flash_min = -1;             // -1: not read yet
@@ -19,11 +20,14 @@ size_t fattn_wsize(int64_t N, int64_t H, int64_t B, int64_t D) { return N > 32 ?
 // q F32 [D, N, H, B]; k [D, n_kv, Hkv, B]; v: vl 0 [D, n_kv, Hkv, B], vl 1 [n_kv(ML), D, Hkv, B] (F16); mask F16 [n_kv, N, ..] or null;
 // causal_past >= 0 (no mask tensor): position kv is visible to query n iff kv <= causal_past + n.
 // dst element (dv, h, n, b) at dst.data + n * nbn + h * nbh + b * nbb.  CLLM_E_UNSUPPORTED: a shape / layout this kernel does not take.
+// cap: the logit soft-cap (0: none); fattn_cap.hip has it at D = 128 / 256 with V rows by position and no causal_past.
 int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, const tview & v, int vl, const tview * mask, int causal_past,
-                 char * dst, int64_t nbn, int64_t nbh, int64_t nbb, float scale, void * wdata, size_t wsize) {
+                 char * dst, int64_t nbn, int64_t nbh, int64_t nbb, float scale, float cap, void * wdata, size_t wsize) {
     const int64_t D = q.ne[0], N = q.ne[1], H = q.ne[2], B = q.ne[3], n_kv = k.ne[1], Hkv = k.ne[2];
     const bool hs = D == 96 || D == 256;                   // fattn_hs.hip (V rows by position only)
     const bool pad = D == 112;                             // fattn_pad.hip (V rows by position only, F16)
+    if (!(cap >= 0.0f) || isinf(cap) || (cap != 0.0f && !isfinite(scale / cap))) FAIL(CLLM_E_INVALID, "flash_attn_ext: logit_softcap %g (scale %g)", (double) cap, (double) scale);
+    if (cap != 0.0f && !((D == 128 || D == 256) && vl == 0 && causal_past < 0)) return CLLM_E_UNSUPPORTED;
     if (D != 64 && D != 128 && !((hs || pad) && vl == 0)) return CLLM_E_UNSUPPORTED;
     if (k.ne[0] != D || (vl == 0 ? v.ne[0] != D || v.ne[1] != n_kv : v.ne[1] != D || v.ne[0] < n_kv) || v.ne[2] != Hkv || Hkv <= 0 || H % Hkv || k.ne[3] != B || v.ne[3] != B) return CLLM_E_UNSUPPORTED;
     if (ktype != CLLM_TYPE_F16 && ktype != CLLM_TYPE_Q8_0) return CLLM_E_UNSUPPORTED;
@@ -50,7 +54,8 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
         mmode = 2;
     } else if (causal_past >= 0) mmode = 1;
     a.dst = dst; a.d_nbn = nbn; a.d_nbh = nbh; a.d_nbb = nbb;
-    a.N = (int) N; a.H = (int) H; a.Hkv = (int) Hkv; a.n_kv = (int) n_kv; a.n_past = causal_past; a.sc2 = scale * FA_LOG2E;
+    a.N = (int) N; a.H = (int) H; a.Hkv = (int) Hkv; a.n_kv = (int) n_kv; a.n_past = causal_past; a.sc2 = scale * FA_LOG2E; a.cap_in = 0.0f;
+    if (cap != 0.0f) { a.cap_in = scale / cap; a.sc2 = cap * FA_LOG2E; }      // the kernel's scores are tanh(s cap_in): their scale is the cap
     const int r = (int)(H / Hkv);
     const bool decode = N * r <= 32;
     a.R = decode ? r : 1;
@@ -67,6 +72,7 @@ int launch_fattn(hipStream_t st, const tview & q, const tview & k, int ktype, co
         }
     }
     if (vl == 1 && (v.nb[1] / 2) % 8) return CLLM_E_UNSUPPORTED;
+    if (cap != 0.0f) return fattn_cap_launch(st, a, (int) D, ktype, mmode, (int) B, decode);
     if (hs) return fattn_hs_launch(st, a, (int) D, ktype, mmode, (int) B, decode);
     if (pad) return fattn_pad_launch(st, a, (int) D, ktype, mmode, (int) B, decode);
     if (D == 128) return fattn_dispatch<128>(st, a, ktype, vl, mmode, (int) B, decode);
@@ -122,7 +128,7 @@ int launch_attn_long_flash(hipStream_t st, const float * qkv, const int32_t * po
     a.mask = nullptr; a.m_nb1 = a.m_nb2 = a.m_nb3 = 0; a.m_ne2 = a.m_ne3 = 1; a.m_al = 0;
     a.dst = (char *) att; a.d_nbn = (int64_t) nh * hd * 4; a.d_nbh = (int64_t) hd * 4; a.d_nbb = a.d_nbn;
     a.part = (float *)((char *) S + q_bytes);
-    a.N = 1; a.H = nh; a.Hkv = nkv; a.R = nh / nkv; a.n_kv = (int) ML; a.n_past = -1; a.sc2 = (1.0f / sqrtf((float) hd)) * FA_LOG2E;
+    a.N = 1; a.H = nh; a.Hkv = nkv; a.R = nh / nkv; a.n_kv = (int) ML; a.n_past = -1; a.sc2 = (1.0f / sqrtf((float) hd)) * FA_LOG2E; a.cap_in = 0.0f;
     a.n_kv_dev = pos_dev;
     const int tiles = (int)((ML + 63) / 64);
     int per = (tiles + max_splits - 1) / max_splits; if (per < tiles / 32) per = tiles / 32; if (per < 1) per = 1;

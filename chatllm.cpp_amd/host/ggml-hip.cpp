@@ -430,7 +430,9 @@ bool dev_supports_op(ggml_backend_dev_t, const ggml_tensor * op) {
         case GGML_OP_FLASH_ATTN_EXT: {      // what cllm_op_flash_attn_ext takes (`-fa`, src/layers.cpp:2634-2656); anything else stays on the CPU backend
             const ggml_tensor * v = op->src[2], * m = op->src[3];
             float max_bias, softcap; memcpy(&max_bias, (const float *) op->op_params + 1, 4); memcpy(&softcap, (const float *) op->op_params + 2, 4);
-            if (!a || !b || !v || op->src[4] || max_bias != 0.0f || softcap != 0.0f || op->type != GGML_TYPE_F32 || a->type != GGML_TYPE_F32 || a->nb[0] != 4) return false;
+            // a logit soft-cap (Gemma-2 on: 50, Grok: 30): launch_fattn's own conditions, head sizes 128 / 256 and a finite cap > 0 (scale / cap is checked at run time)
+            if (softcap != 0.0f && (!(softcap > 0.0f) || std::isinf(softcap) || !a || (a->ne[0] != 128 && a->ne[0] != 256))) return false;
+            if (!a || !b || !v || op->src[4] || max_bias != 0.0f || op->type != GGML_TYPE_F32 || a->type != GGML_TYPE_F32 || a->nb[0] != 4) return false;
             if (b->type != v->type || (b->type != GGML_TYPE_F16 && b->type != GGML_TYPE_Q8_0) || b->nb[0] != ggml_type_size(b->type) || v->nb[0] != ggml_type_size(v->type)) return false;
             const int64_t D = a->ne[0];
             if ((D != 64 && D != 96 && D != 112 && D != 128 && D != 256) || (D % 32 && b->type != GGML_TYPE_F16) || b->ne[0] != D || v->ne[0] != D || v->ne[1] != b->ne[1] || b->ne[2] <= 0 || a->ne[2] % b->ne[2] || v->ne[2] != b->ne[2] || a->ne[3] != b->ne[3] || a->ne[3] != v->ne[3]) return false;

@@ -259,7 +259,9 @@ CLLM_API int cllm_op_scale_mask_soft_max(void * stream, const cllm_tensor * src,
 /* GGML_OP_FLASH_ATTN_EXT  ggml_compute_forward_flash_attn_ext_f16 (ggml-cpu/ops.cpp:8114-8344, tiled :8346-8640, split-KV :8642-8770),
  * as CoreAttention emits it with `-fa` (src/layers.cpp:2634-2656):  dst[:, h, n] = soft_max_kv(scale * K.q + mask) . V
  * q F32 [D, N, H, B] (rows dense); k, v: F16 or Q8_0 [D, n_kv, Hkv, B] rows (--cache_dtype, src/layers.cpp:2925-2945); mask NULL or
- * F16 [n_kv, >= N, 1|H, 1|B]; dst F32 [D, H, N, B] contiguous.  D = 64 | 96 | 112 | 128 | 256 (96 and 256: fattn_hs.hip; 112, F16 k / v only: fattn_pad.hip), H % Hkv == 0, max_bias == 0 and logit_softcap == 0
+ * F16 [n_kv, >= N, 1|H, 1|B]; dst F32 [D, H, N, B] contiguous.  D = 64 | 96 | 112 | 128 | 256 (96 and 256: fattn_hs.hip; 112, F16 k / v only: fattn_pad.hip), H % Hkv == 0, max_bias == 0.
+ * logit_softcap c > 0: the score is c * tanh(scale / c * K.q) + mask (Gemma-2 on: 50, Grok: 30), at D = 128 | 256 (fattn_cap.hip), the tanh on the
+ * hardware's exp2 and rcp (a few 1e-7 absolute); 0: no cap; negative, NaN or infinite: CLLM_E_INVALID
  * (anything else: CLLM_E_UNSUPPORTED, the host keeps the node on the CPU).  TOLERANCE tier: Q is converted to K's vec_dot_type as
  * on the CPU (fp16, or quantize_row_q8_0), scores and the online soft-max are fp32, P is rounded to fp16 for the P.V product; the
  * CPU op itself changes summation order with shape and thread count.  wdata: cllm_flash_attn_wsize() bytes (split-KV partials). */

@@ -3,7 +3,9 @@
 
 Then (alone with the argument `112`) the head size 112 (F16 rows only) beside the kernel whose P.V work it issues, 128, at equal H * D = 7168 (H 64 | 56),
 and 96 at 5760 (H 60) for the line through the two unpadded kernels; H % 4 == 0, three rounds, the sizes alternating inside a round.  The rates count
-useful FLOPs (D, not the padded feature count)."""
+useful FLOPs (D, not the padded feature count).
+
+With the argument `softcap` alone: the prefill at 128 and 256 with logit_softcap 50 and with 0, alternating, three runs each."""
 import ctypes as C
 import os
 import sys
@@ -50,7 +52,7 @@ def kv(r, kv_t, D, n_kv, Hkv, s):
     return T.from_numpy(FM.q8_0_quantize(x).reshape(-1), gpu.Q8_0, [D, n_kv, Hkv]), D // 32 * 34
 
 
-def run(D, kv_t, N, n_kv, mask, HD=6144):
+def run(D, kv_t, N, n_kv, mask, HD=6144, cap=0.0):
     H = HD // D
     Hkv = H // 4
     r = np.random.default_rng(D + N)
@@ -58,8 +60,8 @@ def run(D, kv_t, N, n_kv, mask, HD=6144):
     k, rb = kv(r, kv_t, D, n_kv, Hkv, 0.5)
     v, _ = kv(r, kv_t, D, n_kv, Hkv, 1.0)
     dst = T(gpu.F32, [D, H, N])
-    name = "F16 " if kv_t == FM.F16 else "Q8_0"
-    fn = lambda: ops.flash_attention(q, k, v, mask, 1.0 / np.sqrt(D), dst=dst)
+    name = ("F16 " if kv_t == FM.F16 else "Q8_0") + (f" cap {cap:g}" if cap else "")
+    fn = lambda: ops.flash_attention(q, k, v, mask, 1.0 / np.sqrt(D), logit_softcap=cap, dst=dst)
     if N > 1:
         med, lo, hi = median_ms(fn)
         fl = 4.0 * N * n_kv * D * H / 2
@@ -74,6 +76,12 @@ N = 4096
 m = np.zeros((N, N), np.float16)
 m[np.triu_indices(N, 1)] = -np.inf
 dm = T.from_numpy(m, gpu.F16, [N, N])
+if sys.argv[1:] == ["softcap"]:           # what the logit soft-cap costs: the same shapes with cap 50 and without, alternating, three runs each
+    for D in (128, 256):
+        for _ in range(3):
+            for cap in (50.0, 0.0):
+                run(D, FM.F16, N, N, dm, cap=cap)
+    sys.exit(0)
 if sys.argv[1:] != ["112"]:
     for kv_t in (FM.F16, FM.Q8_0):
         for D in (128, 96, 256):
